@@ -10,12 +10,12 @@ if [ "${1:-}" != "quick" ]; then
   python -m pytest tests -m gpu -q 2>&1 | tail -6 > $O/r05_gpu_tests.txt
   python -c "import __graft_entry__ as g; g.smoke()" >> $O/r05_gpu_tests.txt 2>&1
 fi
-python bench.py > $O/r05_bench_n1.json 2> $O/r05_bench_n1.err
+python bench.py --full > $O/r05_bench_n1.json 2> $O/r05_bench_n1.err
 # rocprofv3 kernel trace of the bench command (LM leg only)
 rm -rf $O/prof_r05
-rocprofv3 --kernel-trace --stats -d $O/prof_r05 -o bench -- python bench.py --no-cpu-baseline --no-frontend > $O/r05_bench_under_rocprof.json 2> $O/r05_rocprof.err
+rocprofv3 --kernel-trace --stats -d $O/prof_r05 -o bench -- python bench.py --full --no-cpu-baseline --no-frontend > $O/r05_bench_under_rocprof.json 2> $O/r05_rocprof.err
 DB=$(find $O/prof_r05 -name "*.db" | head -1)
-python scripts/rocprof_summary.py "$DB" $O/r05_kernel_stats.txt "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-frontend" > /dev/null 2>> $O/r05_rocprof.err
+python scripts/rocprof_summary.py "$DB" $O/r05_kernel_stats.txt "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-frontend" > /dev/null 2>> $O/r05_rocprof.err
 # PMC passes: one counter group per run (no trace domains next to --pmc)
 for grp in "SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES" "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do
   tag=$(echo $grp | cut -d' ' -f1)

@@ -1,8 +1,9 @@
+O=${1:?usage: bash scripts/r06_gpu12.sh OUT_DIR}; mkdir -p $O
 python -m pytest tests/test_gpu_window.py tests/test_native_formulation.py -x -q -m gpu 2>&1 | tail -5
-python bench.py --no-cpu-baseline > gpurun_out/r06_bench_window.json 2> gpurun_out/r06_bench_window.err
-python - <<'PY'
-import json
-d=json.loads(open('gpurun_out/r06_bench_window.json').read().strip().splitlines()[-1])
+python bench.py --full --no-cpu-baseline > $O/r06_bench_window.json 2> $O/r06_bench_window.err
+python - $O/r06_bench_window.json <<'PY'
+import json, sys
+d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 w=d['sliding_window']; b=d['backend_loop']
 print('value', d['value'])
 print('window deferred: host', w['host_ms_mean'], 'update mean/max', w['update_ms_mean'], w['update_ms_max'], 'lm', w['lm_ms_mean'], 'behind', w['frame_behind_a_window'])

@@ -7,6 +7,6 @@ print('%-22s %.1f it/s  %.4f ms/step  repeats %s | fetch wait %.0f us  gap mean 
 rocm-smi --showclocks 2>/dev/null | grep -E "sclk|fclk" >> $O
 for idle in 0 20 0 40 0 20; do
   sleep $idle
-  python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-frontend 2>/dev/null | TAG="after ${idle}s idle" line >> $O
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-frontend 2>/dev/null | TAG="after ${idle}s idle" line >> $O
 done
 cat $O
