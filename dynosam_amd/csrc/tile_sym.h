@@ -459,6 +459,67 @@ struct TileSym {
   }
 };
 
+// Selected inversion (marginal covariances, selinv_tiles.h).  The factorisation leaves S = M~ D M~^T with M~ unit-lower (off-diagonal
+// blocks M(I,K) = A(I,K) T_K^-1, stored by the diagonal-target updates) and D = diag(T_K); Z = S^-1 on the tile pattern follows from the
+// root of the elimination tree down:
+//     Z(I,K) = - sum_{J in R(K)} Zsym(I,J) M(J,K)          every I in R(K)            (Zsym(I,J) = Z(J,I)^T when I < J)
+//     Z(K,K) = T_K^-1 - sum_{J in R(K)} M(J,K)^T Z(J,K)    then symmetrised
+// Every Z tile column K reads lies in an ancestor column (R(K) is a subset of the ancestors, and fill puts every pair of R(K) on the
+// pattern), so the launches go by depth (distance from the root): off-diagonal targets of depth d, then the diagonal tiles of depth d.
+// Sources are listed in ascending J: every tile is the same sequence of operations whatever else is computed (bit-identical subsets).
+struct SelTask { int32_t tgt, src0, nsrc, col; };   // tgt: tile id of Z(I,K) (off-diagonal launch) or of Z(K,K) (diagonal launch)
+struct SelSrc { int32_t z, m, tr, pad; };           // Z tile id, M tile id; tr: the Z tile enters transposed (off-diagonal: Z(J,I)^T)
+struct SelSchedule {
+  std::vector<SelTask> task;
+  std::vector<SelSrc> src;
+  std::vector<int32_t> launch;   // [n_launch + 1] task ranges; launch 2d = off-diagonal targets of depth d, 2d + 1 = its diagonal tiles
+  std::vector<uint8_t> need;     // the columns computed: the requested ones and every ancestor
+  int64_t products = 0;          // 32x32x32 tile products (2 * 32^3 flops each)
+
+  // need_in[K] != 0: column K is requested (closed under the parent here); empty: every column
+  void build(const TileSym& s, const std::vector<uint8_t>& need_in) {
+    const int nt = s.nt;
+    need.assign(nt, need_in.empty() ? 1 : 0);
+    for (int K = 0; K < nt && !need_in.empty(); ++K)
+      if (need_in[K])
+        for (int J = K; J >= 0 && !need[J]; J = s.parent[J]) need[J] = 1;
+    std::vector<int32_t> depth(nt, 0);
+    int maxd = -1;
+    for (int K = nt - 1; K >= 0; --K) {   // (parent(K) > K)
+      depth[K] = s.parent[K] >= 0 ? depth[s.parent[K]] + 1 : 0;
+      if (need[K]) maxd = std::max(maxd, (int)depth[K]);
+    }
+    std::vector<std::vector<int32_t>> by_depth((size_t)maxd + 1);
+    for (int K = 0; K < nt; ++K) if (need[K]) by_depth[depth[K]].push_back(K);
+    task.clear(); src.clear(); launch.assign(1, 0); products = 0;
+    for (int d = 0; d <= maxd; ++d) {
+      for (int K : by_depth[d]) {
+        const int32_t b = s.col_ptr[K] + 1, e = s.col_ptr[K + 1];
+        for (int32_t x = b; x < e; ++x) {
+          const int I = s.row_idx[x];
+          task.push_back({x, (int32_t)src.size(), e - b, K});
+          for (int32_t y = b; y < e; ++y) {
+            const int J = s.row_idx[y];
+            if (I == J) src.push_back({s.diag(I), y, 0, 0});
+            else if (I > J) src.push_back({s.find(I, J), y, 0, 0});
+            else src.push_back({s.find(J, I), y, 1, 0});
+          }
+          products += e - b;
+        }
+      }
+      launch.push_back((int32_t)task.size());
+      for (int K : by_depth[d]) {
+        const int32_t b = s.col_ptr[K] + 1, e = s.col_ptr[K + 1];
+        task.push_back({s.diag(K), (int32_t)src.size(), e - b, K});
+        for (int32_t y = b; y < e; ++y) src.push_back({y, y, 0, 0});
+        products += e - b;
+      }
+      launch.push_back((int32_t)task.size());
+    }
+    if (src.empty()) src.push_back({0, 0, 0, 0});
+  }
+};
+
 // Elimination order of the pose-like variables.  `sorted` = variables sorted by (frame, key);
 // pos[k] = elimination position of entry k, off[p] = scalar row/column of the first tangent
 // component of the variable at position p.
