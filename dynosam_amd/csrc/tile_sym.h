@@ -520,6 +520,82 @@ struct SelSchedule {
   }
 };
 
+// Joint marginals (joint_tiles.h): X = S^-1 G for a few dense right-hand sides G on the same factor S = M~ D M~^T,
+//     forward   Y_K = G_K - sum_{J < K, (K,J) on the pattern} M(K,J) Y_J      (fused with)  W_K = T_K^-1 Y_K
+//     backward  X_K = W_K - sum_{I in R(K)} M(I,K)^T X_I
+// G is supported on a set of tile columns; C is that set closed under the parent.  Y vanishes outside C (a source J of row K has K
+// as an ancestor), and X on C needs X on C only (R(K) holds ancestors), so both passes run over C alone: the forward pass by height
+// in C (children first), the backward pass by depth in C (root first; a root has no sources and keeps X = W, so depth 0 needs no
+// launch).  The right-hand sides are cut into nb column blocks of 32; Y and X are panels of 32x32 tiles, panel p = b |C| + slot(K),
+// and every launch lists its tasks block by block (b outer): a batch of the first nbb < nb blocks runs the first nbb / nb of each
+// launch.  Sources in ascending tile column: a column of X is the same sequence of operations whichever block it rides in.
+struct JointTask { int32_t tgt, src0, nsrc, col; };   // tgt: panel of (K, b); col: K (its T_K^-1 in the forward pass)
+struct JointSrc { int32_t a, b, tr, pad; };           // a: tile id of M (forward M(K,J), backward M(I,K), tr = 1: enters transposed), b: source panel
+struct JointSchedule {
+  std::vector<uint8_t> need;     // C: the support and every ancestor
+  std::vector<int32_t> cols;     // C ascending
+  std::vector<int32_t> slot;     // [nt] position in cols, -1 outside C
+  std::vector<JointTask> task;
+  std::vector<JointSrc> src;
+  std::vector<int32_t> launch;   // [n_fwd + n_bwd + 1] task ranges: the forward launches (height 0 first), then the backward ones (depth 1 first)
+  int n_fwd = 0, n_bwd = 0, nb = 0;
+  int64_t products = 0;          // 32x32x32 tile products of all nb blocks (T_K^-1 Y_K included)
+
+  // support[K] != 0: column K holds a non-zero row of G (closed under the parent here)
+  void build(const TileSym& s, const std::vector<uint8_t>& support, int nb_) {
+    const int nt = s.nt;
+    nb = nb_;
+    need.assign(nt, 0);
+    for (int K = 0; K < nt; ++K)
+      if (support[K])
+        for (int J = K; J >= 0 && !need[J]; J = s.parent[J]) need[J] = 1;
+    cols.clear(); slot.assign(nt, -1);
+    for (int K = 0; K < nt; ++K) if (need[K]) { slot[K] = (int32_t)cols.size(); cols.push_back(K); }
+    const int32_t nc = (int32_t)cols.size();
+    // row view of the pattern inside C: (K, J) tiles of row K, ascending J
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> row(nc);   // (J, tile id)
+    for (int J : cols)
+      for (int32_t x = s.col_ptr[J] + 1; x < s.col_ptr[J + 1]; ++x) row[slot[s.row_idx[x]]].push_back({J, x});
+    std::vector<int32_t> height(nt, 0), depth(nt, 0);
+    int maxh = -1, maxd = -1;
+    for (int K : cols) {   // (parent(K) > K: ascending K sees every child first)
+      maxh = std::max(maxh, (int)height[K]);
+      if (s.parent[K] >= 0) height[s.parent[K]] = std::max(height[s.parent[K]], height[K] + 1);
+    }
+    for (int q = nc - 1; q >= 0; --q) {
+      const int K = cols[q];
+      depth[K] = s.parent[K] >= 0 ? depth[s.parent[K]] + 1 : 0;
+      maxd = std::max(maxd, (int)depth[K]);
+    }
+    std::vector<std::vector<int32_t>> by_h((size_t)maxh + 1), by_d((size_t)maxd + 1);
+    for (int K : cols) { by_h[height[K]].push_back(K); by_d[depth[K]].push_back(K); }
+    task.clear(); src.clear(); launch.assign(1, 0); products = 0;
+    for (int h = 0; h <= maxh; ++h) {
+      for (int b = 0; b < nb; ++b)
+        for (int K : by_h[h]) {
+          const auto& r = row[slot[K]];
+          task.push_back({b * nc + slot[K], (int32_t)src.size(), (int32_t)r.size(), K});
+          for (auto& jx : r) src.push_back({jx.second, b * nc + slot[jx.first], 0, 0});
+          products += (int64_t)r.size() + 1;
+        }
+      launch.push_back((int32_t)task.size());
+    }
+    n_fwd = maxh + 1;
+    for (int d = 1; d <= maxd; ++d) {
+      for (int b = 0; b < nb; ++b)
+        for (int K : by_d[d]) {
+          const int32_t x0 = s.col_ptr[K] + 1, x1 = s.col_ptr[K + 1];
+          task.push_back({b * nc + slot[K], (int32_t)src.size(), x1 - x0, K});
+          for (int32_t x = x0; x < x1; ++x) src.push_back({x, b * nc + slot[s.row_idx[x]], 1, 0});
+          products += x1 - x0;
+        }
+      launch.push_back((int32_t)task.size());
+    }
+    n_bwd = std::max(0, maxd);
+    if (src.empty()) src.push_back({0, 0, 0, 0});
+  }
+};
+
 // Elimination order of the pose-like variables.  `sorted` = variables sorted by (frame, key);
 // pos[k] = elimination position of entry k, off[p] = scalar row/column of the first tangent
 // component of the variable at position p.
