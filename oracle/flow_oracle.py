@@ -91,6 +91,39 @@ def corr_argmax(da_bits: np.ndarray, db_bits: np.ndarray, w: int, h: int, R: int
     return best.astype(np.int32), C
 
 
+CORR_G = 63 * 2.0 ** -24 * 1.008   # bound on |float32 sum of the 64 exact products, in any order - exact sum| for unit-norm bf16 rows
+
+
+def corr_argmax_f64(da_bits: np.ndarray, db_bits: np.ndarray, w: int, h: int, R: int, got=None):
+    """`corr_argmax` with the sum in float64: the products of two bf16 numbers are exact in float64 and a sum of 64 of them rounds
+    by about 1e-16, so this is the arg-max the kernel's rules (window |dx|,|dy| <= R, ties -> lowest q, no positive score -> q = p)
+    give in exact arithmetic, free of any float32 accumulation order.  Row by row (the full n x n float64 matrix is never held).
+    With `got` (another matcher's answer for every p, each inside p's window) also returns, per p, how far the float64 score of
+    `got[p]` lies below the float64 maximum (0 where they agree).  The fall-back q = p counts as a score of 0 on either side.
+    returns best [n] int32, or (best, deficit [n] float64)."""
+    A, B = bf16_to_f32(da_bits).astype(np.float64), bf16_to_f32(db_bits).astype(np.float64)
+    n = w * h
+    best = np.zeros(n, np.int32)
+    deficit = np.zeros(n, np.float64)
+    for p in range(n):
+        x, y = p % w, p // w
+        xs, ys = np.arange(max(0, x - R), min(w - 1, x + R) + 1), np.arange(max(0, y - R), min(h - 1, y + R) + 1)
+        q = (ys[:, None] * w + xs[None, :]).ravel()          # ascending q: argmax takes the lowest index among equals
+        c = B[q] @ A[p]
+        k = int(c.argmax())
+        top = c[k]
+        best[p] = q[k] if top > 0 else p
+        if got is not None and int(got[p]) != int(best[p]):
+            g = int(got[p])
+            assert abs(g % w - x) <= R and abs(g // w - y) <= R, (p, g)
+            sg = float(B[g] @ A[p])
+            if top > 0:      # it chose g, or (g == p) may have seen nothing positive and fallen back: "nothing" scores 0
+                deficit[p] = top - (max(sg, 0.0) if g == p else sg)
+            else:            # exact arithmetic sees nothing positive; it saw a positive score at g
+                deficit[p] = 0.0 - sg
+    return best if got is None else (best, deficit)
+
+
 def _cost(pa, B, xs, ys, fx, fy, dx, dy):
     h, w = B.shape
     c = np.zeros(xs.shape, F32)

@@ -47,3 +47,39 @@ def test_shrunken_image_test_uses_truncated_coordinates():
     flow = np.zeros((H, W, 2), np.float32); flow[..., 0] = 20.0; flow[..., 1] = 0.25
     r = FO.track_dynamic([(20.0, 10.0), (5.0, 10.0)], [1, 1], [0, 0], [0, 1], flow, mask, shrink_row=2, shrink_col=2)
     assert list(r["code"]) == [FO.OUTSIDE_SHRUNKEN, FO.KEPT]
+
+
+def test_fp64_corr_argmax_agrees_with_the_float32_oracle_and_measures_a_planted_error():
+    """oracle/flow_oracle.corr_argmax_f64 (the float64 reference the GPU arg-max is judged by at sizes with padding) against
+    corr_argmax on a small scene whose coarse grid (24 x 17 = 408 cells) is not a multiple of 32, at a narrow, the default and
+    a grid-covering radius.  numpy's float32 sum is within CORR_G of the exact one, so wherever the two disagree the float64
+    score of the float32 choice is within 2 CORR_G of the float64 maximum; a planted wrong match has a deficit far above that.
+    Flat patches (zero descriptors) take the fall-back q = p in both."""
+    sc = SI.make_pair(width=192, height=136, objects=1, seed=3, max_flow=5.0)
+    rgb0 = sc["rgb0"].copy(); rgb0[:, 96:] = 90                                 # a flat half: its cells (zero descriptors) have no positive score
+    p0, p1 = FO.pyramid(rgb0), FO.pyramid(sc["rgb1"])
+    h3, w3 = p0[3].shape
+    assert (w3, h3) == (24, 17)
+    d0, d1 = FO.descriptors(p0[3]), FO.descriptors(p1[3])
+    n = w3 * h3
+    for R in (2, 6, 24):
+        m32, C = FO.corr_argmax(d0, d1, w3, h3, R)
+        m64, deficit = FO.corr_argmax_f64(d0, d1, w3, h3, R, got=m32)
+        assert np.array_equal(FO.corr_argmax_f64(d0, d1, w3, h3, R), m64)
+        differ = m32 != m64
+        assert differ.mean() <= 0.005 and np.all(deficit[~differ] == 0) and np.all(deficit >= 0) and deficit.max() <= 2 * FO.CORR_G, (R, int(differ.sum()), deficit.max())
+        px, py = np.arange(n) % w3, np.arange(n) // w3
+        assert np.all(np.abs(m64 % w3 - px) <= R) and np.all(np.abs(m64 // w3 - py) <= R)
+        # the float64 maximum itself agrees with the float32 matrix to float32 accuracy
+        top32 = C[np.arange(n), m32]
+        top64 = (FO.bf16_to_f32(d0).astype(np.float64) * FO.bf16_to_f32(d1[m64]).astype(np.float64)).sum(1)
+        pos = top32 > 0
+        assert pos.sum() > 200 and (~pos).sum() > 50 and np.all(m64[~pos] == np.arange(n)[~pos])
+        assert np.abs(top32[pos] - top64[pos]).max() <= FO.CORR_G
+        # a planted error: the neighbouring candidate instead of the best one
+        bad = m64.copy()
+        p = int(np.nonzero(pos & (m64 % w3 + 1 < w3) & (np.abs(m64 % w3 + 1 - px) <= R))[0][0])
+        bad[p] = m64[p] + 1
+        _, dbad = FO.corr_argmax_f64(d0, d1, w3, h3, R, got=bad)
+        assert dbad[p] > 1e-3 and np.count_nonzero(dbad) == 1
+    assert 3.7e-6 < FO.CORR_G < 3.9e-6
