@@ -64,4 +64,5 @@ def test_wrapper_checks_its_problem_list_before_any_device_call():
 def test_build_follows_the_new_header():
     from dynosam_amd.csrc import build as B
     d = B.deps(os.path.join(B.HERE, "dynoflow.hip"))
-    assert os.path.join(B.HERE, "pointcloud_ransac.h") in d and os.path.join(B.HERE, "pnp_ransac.h") in d
+    for header in ("pointcloud_ransac.h", "pnp_ransac.h", "relpose_ransac.h", "ransac_batch.h"):
+        assert os.path.join(B.HERE, header) in d, header

@@ -135,7 +135,7 @@ def test_sampler_is_the_first_three_slots_of_the_homography_sampler():
         s = P.sample3(h, 3)
         assert s is None or sorted(s) == [0, 1, 2]
     assert sum(P.sample3(h, 3) is not None for h in range(200)) > 150
-    assert "1315423911" in inspect.getsource(P.sample3)
+    assert "1315423911" in inspect.getsource(P.sample_k) and "sample_k(h, n, 3)" in inspect.getsource(P.sample3)
 
 
 def test_ransac_mask_and_transform_on_noise_free_scenes_with_20_percent_outliers():
