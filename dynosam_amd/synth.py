@@ -62,7 +62,24 @@ def so3_log(R):
     th = np.arccos(c)
     with np.errstate(divide="ignore", invalid="ignore"):
         mag = np.where(tr3 < -1e-6, th / (2.0 * np.sin(th)), 0.5 - tr3 / 12.0 + tr3 * tr3 / 60.0)
-    return mag[..., None] * v
+    om = mag[..., None] * v
+    near_pi = tr + 1.0 < 1e-3
+    if np.any(near_pi):
+        # SO3::Logmap's largest-diagonal case near theta = pi (a select: every other rotation keeps the bits it had)
+        d = np.stack([R[..., 0, 0], R[..., 1, 1], R[..., 2, 2]], -1)
+        k = np.where((d[..., 2] > d[..., 1]) & (d[..., 2] > d[..., 0]), 2, np.where(d[..., 1] > d[..., 0], 1, 0))
+        i1, i2 = (k + 1) % 3, (k + 2) % 3                     # omega[k] = sc Q1, omega[k+1] = sc Q2, omega[k+2] = sc Q3
+        g = lambda a, b: np.take_along_axis(np.take_along_axis(R, a[..., None, None], -2), b[..., None, None], -1)[..., 0, 0]
+        W = g(i2, i1) - g(i1, i2)
+        Q1, Q2, Q3 = 2.0 + 2.0 * g(k, k), g(k, i1) + g(i1, k), g(i2, k) + g(k, i2)
+        sgn = np.where(W < 0, -1.0, 1.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            sc = sgn * 0.5 * (1.0 / np.sqrt(Q1)) * (np.pi - (2.0 * sgn * W) / np.sqrt(Q1 * Q1 + Q2 * Q2 + Q3 * Q3 + W * W))
+        alt = np.zeros_like(om)
+        for c, q in ((k, Q1), (i1, Q2), (i2, Q3)):
+            np.put_along_axis(alt, c[..., None], (sc * q)[..., None], -1)
+        om = np.where(near_pi[..., None], alt, om)
+    return om
 
 
 def se3_exp(xi):
