@@ -1082,14 +1082,24 @@ struct AssembleView {
 };
 
 // pass 1: one wavefront per chunk of <= 64 contributions to ONE 6x6 block. Lanes first fetch the chunk's indices (one
-// contribution per lane, coalesced); the chunk is then walked with the indices broadcast by readlane, one fp64 MFMA
-// (16x16x4) per contribution: the K slots 0..2 carry the 3 columns of the two 6x3 Z rows (slot 3 is zero), the 6x6
-// product sits in the top-left corner of the 16x16 accumulator. Each lane loads ONE double per operand - the vector
-// memory pipeline, not arithmetic, bounds this kernel, and the scalar formulation issued 6 loads per contribution.
+// contribution per lane, coalesced); the chunk is then walked one fp64 MFMA (16x16x4) at a time: the K slots 0..2 carry
+// the 3 columns of the two 6x3 Z rows (slot 3 is zero), the 6x6 product sits in the top-left corner of the 16x16
+// accumulator. The vector memory pipeline, not arithmetic, bounds this kernel.
 // Fixed order => deterministic.
 #ifndef ASM_PAIR_U
 #define ASM_PAIR_U 4
 #endif
+// Schur pairs: the Z rows of ASM_STAGE contributions (ASM_STAGE e1 rows, then ASM_STAGE e2 rows) are fetched by 16-byte
+// wave loads into the wave's own LDS region, and the MFMA operands are read from there. A row is 18 doubles = nine
+// 16-byte pieces, so with row stride 18 piece p of a stage simply lands at byte 16 p. Multiple of 2 * ASM_PAIR_U, <= 64.
+// 16 keeps 8 workgroups per CU (4.6 KB of LDS per wave); a chunk of config 2 holds 20 contributions on average, and the
+// waves lost to a larger stage cost more than its fewer round trips bring (32: 4 per SIMD, 64: 2; measured:
+// profiles/r07_ab_assemble_stage.txt, also with the next stage's loads ahead of the MFMAs - spills under 64 VGPRs).
+#ifndef ASM_STAGE
+#define ASM_STAGE 16
+#endif
+static_assert(ASM_STAGE % (2 * ASM_PAIR_U) == 0 && ASM_STAGE >= 2 * ASM_PAIR_U && ASM_STAGE <= 64, "a stage holds whole MFMA trips of one chunk");
+constexpr int ASM_STAGE_LD = (18 * ASM_STAGE + 63) / 64;   // 16-byte wave loads per stage
 __device__ __forceinline__ void asm_chunks_body(AssembleView A, const double* const* __restrict__ Jpp,
                                                 const double* __restrict__ Z, double* __restrict__ partial, const int bid, const int nblocks) {
   typedef double d4_t __attribute__((ext_vector_type(4)));
@@ -1110,25 +1120,56 @@ __device__ __forceinline__ void asm_chunks_body(AssembleView A, const double* co
     // products land in the diagonal blocks (0..5, 0..5) and (8..13, 8..13) of the 16x16 accumulator (the off-diagonal blocks
     // are never read) and are added at the end: half the loads and half the MFMAs of one contribution per instruction -
     // the kernel is bound by the number of vector-memory instructions, not by bytes or flops.
+    typedef double d2_t __attribute__((ext_vector_type(2)));
+    __shared__ __attribute__((aligned(16))) double zstage[4][36 * ASM_STAGE];
+    double* const zs = zstage[threadIdx.x >> 6];   // this wave's region: no other wave touches it, LDS is in order per wave => no barrier
     int e1 = 0, e2 = 0;
     if (lane < n) { e1 = A.sp_e[2 * (lo + lane)]; e2 = A.sp_e[2 * (lo + lane) + 1]; }
     const int half = ij >> 3, r6 = ij & 7;
     const bool ld = r6 < 6 && g < 3;
     const int zo = ld ? 3 * r6 + g : 0;
-    // ASM_PAIR_U MFMAs (2 contributions each) per trip: their loads are independent and issue back to back
-    for (int k0 = 0; k0 < n; k0 += 2 * ASM_PAIR_U) {
-      double a[ASM_PAIR_U], b[ASM_PAIR_U];
+    // piece p = 64 i + lane of a stage's load i is 16-byte piece p % 9 of staged row p / 9; rows 0 .. ASM_STAGE - 1 are the e1 rows of
+    // contributions s0 .., the next ASM_STAGE their e2 rows.  Contributions >= n are not fetched: their operands are masked below.
+    d2_t v[ASM_STAGE_LD];
+    auto fetch = [&](const int s0) {
 #pragma unroll
-      for (int u = 0; u < ASM_PAIR_U; ++u) {
-        const int ka = k0 + 2 * u;   // lanes >= n hold row 0 (a valid address); masked below
-        const int f1a = __builtin_amdgcn_readlane(e1, ka & 63), f2a = __builtin_amdgcn_readlane(e2, ka & 63);
-        const int f1b = __builtin_amdgcn_readlane(e1, (ka + 1) & 63), f2b = __builtin_amdgcn_readlane(e2, (ka + 1) & 63);
-        const int f1 = half ? f1b : f1a, f2 = half ? f2b : f2a;
-        a[u] = 0.0; b[u] = 0.0;
-        if (ld && ka + half < n) { a[u] = -Z[18 * (int64_t)f1 + zo]; b[u] = Z[18 * (int64_t)f2 + zo]; }
+      for (int i = 0; i < ASM_STAGE_LD; ++i) {
+        const int p = 64 * i + lane, r = p / 9, q = p - 9 * r;
+        const bool second = r >= ASM_STAGE;
+        const int c = s0 + (second ? r - ASM_STAGE : r);
+        const int f1 = __shfl(e1, c & 63), f2 = __shfl(e2, c & 63);
+        const int f = second ? f2 : f1;
+        v[i] = d2_t{0.0, 0.0};
+        if (p < 18 * ASM_STAGE && c < n) v[i] = *reinterpret_cast<const d2_t*>(Z + 18 * (int64_t)f + 2 * q);
       }
+    };
+    fetch(0);
+    for (int s0 = 0; s0 < n; s0 += ASM_STAGE) {
 #pragma unroll
-      for (int u = 0; u < ASM_PAIR_U; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc, 0, 0, 0);
+      for (int i = 0; i < ASM_STAGE_LD; ++i) {
+        const int p = 64 * i + lane;
+        if (p < 18 * ASM_STAGE) *reinterpret_cast<d2_t*>(zs + 2 * p) = v[i];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (compiler ordering only: the lanes below read what other lanes wrote)
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const int s1 = min(s0 + ASM_STAGE, n);
+      // ASM_PAIR_U MFMAs (2 contributions each) per trip
+      for (int k0 = s0; k0 < s1; k0 += 2 * ASM_PAIR_U) {
+        double a[ASM_PAIR_U], b[ASM_PAIR_U];
+#pragma unroll
+        for (int u = 0; u < ASM_PAIR_U; ++u) {
+          const int ka = k0 + 2 * u, row = ka + half - s0;   // row < ASM_STAGE; rows of contributions >= n hold zeros and are masked
+          const double za = zs[18 * row + zo], zb = zs[18 * (ASM_STAGE + row) + zo];
+          const bool on = ld && ka + half < n;
+          a[u] = on ? -za : 0.0; b[u] = on ? zb : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < ASM_PAIR_U; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc, 0, 0, 0);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the next stage's writes stay behind these reads
+      __builtin_amdgcn_wave_barrier();
+      if (s0 + ASM_STAGE < n) fetch(s0 + ASM_STAGE);
     }
     // lane (j, g) holds rows g + 4 r of column j: block one = r 0,1 of columns 0..5, block two = r 2,3 of columns 8..13
     acc[0] += __shfl_down(acc[2], 8, 16);
@@ -1316,8 +1357,9 @@ __global__ __launch_bounds__(256) void k_rhs(RhsView R, const double* const* __r
 // 8 waves per SIMD (64 VGPRs, 5 spilled): the launch is a latency-bound gather, what it needs is waves in flight - 267 -> 239 us for the
 // assembly phase and 1.62 -> 1.58 ms per LM iteration against the 5 waves the unconstrained 70 VGPRs gave (same idea measured on k_edge_z and
 // k_trial_errors_fused: their spills cost more than the extra waves bring)
+// (the staging LDS of the Schur pairs, 4 x 288 ASM_STAGE bytes per workgroup, allows 8 / 4 / 2 workgroups per CU at ASM_STAGE 16 / 32 / 64)
 #ifndef ASM_WAVES
-#define ASM_WAVES 8
+#define ASM_WAVES (ASM_STAGE <= 16 ? 8 : ASM_STAGE <= 32 ? 4 : 2)
 #endif
 __global__ __launch_bounds__(256, ASM_WAVES) void k_assemble_rhs(AssembleView A, RhsView R, const double* const* __restrict__ Jpp, const double* __restrict__ Z,
                                                       const double* __restrict__ uq, double* __restrict__ partial, double* __restrict__ gc, int n_asm) {
