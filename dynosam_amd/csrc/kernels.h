@@ -1079,6 +1079,12 @@ struct AssembleView {
   int nbt;
   const double* prior_L;   // dense Hessian of the marginal prior (row-major, prior_dim^2) or null
   int prior_dim;
+  // direct chunks assembled once per linearisation (k_assemble_direct): the ids of the kind-1 / kind-0 chunks in block order, and
+  // where a chunk's 36 doubles sit - slot s >= 0: at 36 s of the solve set's partial sums, s < 0: at 36 ~s of the linearisation's cache
+  int64_t n_dch, n_sch;
+  const int32_t* dch;
+  const int32_t* sch;
+  const int32_t* ch_slot;
 };
 
 // pass 1: one wavefront per chunk of <= 64 contributions to ONE 6x6 block. Lanes first fetch the chunk's indices (one
@@ -1100,22 +1106,27 @@ struct AssembleView {
 #endif
 static_assert(ASM_STAGE % (2 * ASM_PAIR_U) == 0 && ASM_STAGE >= 2 * ASM_PAIR_U && ASM_STAGE <= 64, "a stage holds whole MFMA trips of one chunk");
 constexpr int ASM_STAGE_LD = (18 * ASM_STAGE + 63) / 64;   // 16-byte wave loads per stage
-__device__ __forceinline__ void asm_chunks_body(AssembleView A, const double* const* __restrict__ Jpp,
+// MODE 0: every chunk, its sums at 36 * (chunk id); 1: the Schur-pair chunks alone (A.sch), 2: the direct chunks alone (A.dch) - sums at
+// 36 * (position in that list).  The arithmetic of a chunk is the same in every mode.  MODE 1 never reads the records (Jbuf may be null),
+// MODE 2 never reads Z.
+template <int MODE>
+__device__ __forceinline__ void asm_chunks_body(AssembleView A, const double* __restrict__ Jbuf,
                                                 const double* __restrict__ Z, double* __restrict__ partial, const int bid, const int nblocks) {
   typedef double d4_t __attribute__((ext_vector_type(4)));
-  const double* __restrict__ Jbuf = *Jpp;
   // chunks are sorted by block (row pose, column pose): workgroup ids round-robin over the 8 XCDs, so give every XCD one
   // contiguous eighth of the chunk list - its L2 then holds the Z rows of "its" poses (grid = 8 * per)
   const int64_t per = nblocks >> 3;
   const int64_t wg = (int64_t)(bid & 7) * per + (bid >> 3);
-  const int64_t ch = wg * 4 + (threadIdx.x >> 6);
+  const int64_t slot = wg * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (ch >= A.n_chunk) return;
+  if (slot >= (MODE == 0 ? A.n_chunk : MODE == 1 ? A.n_sch : A.n_dch)) return;
+  const int64_t ch = MODE == 0 ? slot : MODE == 1 ? A.sch[slot] : A.dch[slot];
+  const bool schur = MODE == 1 || (MODE == 0 && A.ch_kind[ch] == 0);
   const int n = A.ch_n[ch], lo = A.ch_lo[ch];
   const int ij = lane & 15, g = lane >> 4;       // operand row (A: i, B: j) and K slot
   const bool act = ij < 6;
   d4_t acc = {0.0, 0.0, 0.0, 0.0};
-  if (A.ch_kind[ch] == 0) {
+  if (schur) {
     // TWO contributions per MFMA: operand rows 0..5 carry contribution 2m, rows 8..13 contribution 2m + 1, so the two 6x6
     // products land in the diagonal blocks (0..5, 0..5) and (8..13, 8..13) of the 16x16 accumulator (the off-diagonal blocks
     // are never read) and are added at the end: half the loads and half the MFMAs of one contribution per instruction -
@@ -1235,18 +1246,25 @@ __device__ __forceinline__ void asm_chunks_body(AssembleView A, const double* co
   }
   // accumulator: lane (j = lane & 15, g = lane >> 4) holds rows g + 4 r, r = 0..3, of column j
   if (act) {
-    partial[ch * 36 + 6 * g + ij] = acc[0];
-    if (g < 2) partial[ch * 36 + 6 * (4 + g) + ij] = acc[1];
+    partial[slot * 36 + 6 * g + ij] = acc[0];
+    if (g < 2) partial[slot * 36 + 6 * (4 + g) + ij] = acc[1];
   }
 }
 __global__ __launch_bounds__(256) void k_assemble_chunks(AssembleView A, const double* const* __restrict__ Jpp,
                                                          const double* __restrict__ Z, double* __restrict__ partial) {
-  asm_chunks_body(A, Jpp, Z, partial, (int)blockIdx.x, (int)gridDim.x);
+  asm_chunks_body<0>(A, *Jpp, Z, partial, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // pass 2: one lane per (block, element): sum the block's chunk partials in order, add damping, store
+// (dpp: null, or the solve set's slot pair {records, cache} of the linearisation - the direct chunks' sums are then read from the cache)
+__device__ __forceinline__ double chunk_sum(const AssembleView& A, const double* __restrict__ partial, const double* __restrict__ dpart, const int c, const int el, bool& direct) {
+  if (!dpart) { direct = A.ch_kind[c] == 1; return partial[(int64_t)c * 36 + el]; }
+  const int s = A.ch_slot[c];
+  direct = s < 0;
+  return direct ? dpart[(int64_t)~s * 36 + el] : partial[(int64_t)s * 36 + el];
+}
 __global__ void k_assemble_final(AssembleView A, const double* __restrict__ partial, const double* __restrict__ lambda_p,
-                                 double add_lambda, double* __restrict__ Sb) {
+                                 double add_lambda, double* __restrict__ Sb, const double* const* __restrict__ dpp = nullptr) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t blk = t / 36;
   const int el = (int)(t % 36);
@@ -1254,7 +1272,8 @@ __global__ void k_assemble_final(AssembleView A, const double* __restrict__ part
   const int i = el / 6, j = el % 6;
   const int a = A.blk_a[blk], b = A.blk_b[blk];
   double acc = (a == b && i == j) ? add_lambda * (*lambda_p) : 0.0;
-  for (int c = A.blk_ch[blk]; c < A.blk_ch[blk + 1]; ++c) acc += partial[(int64_t)c * 36 + el];
+  const double* __restrict__ dpart = dpp ? dpp[1] : nullptr;
+  for (int c = A.blk_ch[blk]; c < A.blk_ch[blk + 1]; ++c) { bool direct; acc += chunk_sum(A, partial, dpart, c, el, direct); }
   const int gi = 6 * a + i, gj = 6 * b + j;
   if (gi >= gj) Sb[band_addr(gi, gj, A.nbt)] = acc;
 }
@@ -1265,7 +1284,7 @@ __global__ void k_assemble_final(AssembleView A, const double* __restrict__ part
 __global__ void k_assemble_final_tiles(AssembleView A, const double* __restrict__ partial, const double* __restrict__ lambda_p,
                                        double add_lambda, const int32_t* __restrict__ off, const int32_t* __restrict__ blk_tile,
                                        double* __restrict__ At, double* __restrict__ raw_int = nullptr, double* __restrict__ raw_sep = nullptr,
-                                       int raw_split = 0, double* __restrict__ hdiag = nullptr) {
+                                       int raw_split = 0, double* __restrict__ hdiag = nullptr, const double* const* __restrict__ dpp = nullptr) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t blk = t / 36;
   const int el = (int)(t % 36);
@@ -1276,10 +1295,12 @@ __global__ void k_assemble_final_tiles(AssembleView A, const double* __restrict_
   const bool dg = a == b && i == j, ddamp = lambda_p[1] != 0.0;
   double acc = (dg && !ddamp) ? add_lambda * (*lambda_p) : 0.0;
   double raw = 0.0;   // diagonal of the un-reduced J^T J: the DIRECT contributions of the block (factors and the dense prior), not the Schur pairs
+  const double* __restrict__ dpart = dpp ? dpp[1] : nullptr;
   for (int c = A.blk_ch[blk]; c < A.blk_ch[blk + 1]; ++c) {
-    const double v = partial[(int64_t)c * 36 + el];
+    bool direct;
+    const double v = chunk_sum(A, partial, dpart, c, el, direct);
     acc += v;
-    if (A.ch_kind[c] == 1) raw += v;
+    if (direct) raw += v;
   }
   if (dg && ddamp) acc += add_lambda * lm_damp(*lambda_p, true, raw);
   const int oa = off[a], ob = off[b];
@@ -1309,13 +1330,21 @@ struct RhsView {
 };
 
 // one wavefront per pose; fixed lane partition + butterfly reduction => deterministic
-__device__ __forceinline__ void rhs_body(RhsView R, const double* const* __restrict__ Jpp, const double* __restrict__ Z,
-                                         const double* __restrict__ uq, double* __restrict__ gc, const int bid) {
-  const double* __restrict__ Jbuf = *Jpp;
+// MODE 0: both loops; 2: the factor loop alone (it needs the records only), every LANE's six sums go to glane[(6 a + c) * 64 + lane];
+// 1: the lanes start from those sums (glane_in) and run the edge loop - lane by lane the same operations in the same order as MODE 0.
+// MODE 1 never touches the records (its callers pass Jbuf = nullptr), MODE 2 never touches Z, uq and gc.
+template <int MODE>
+__device__ __forceinline__ void rhs_body(RhsView R, const double* __restrict__ Jbuf, const double* __restrict__ Z,
+                                         const double* __restrict__ uq, double* __restrict__ gc, const int bid, double* __restrict__ glane = nullptr,
+                                         const double* __restrict__ glane_in = nullptr) {
   const int64_t a = (int64_t)bid * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (a >= R.n_pose) return;
   double g[6] = {0, 0, 0, 0, 0, 0};
+  if (MODE == 1) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) g[c] = glane_in[(6 * a + c) * 64 + lane];
+  } else
   for (int k = R.pi_ptr[a] + lane; k < R.pi_ptr[a + 1]; k += 64) {
     const double* A = Jbuf + R.pi_a[k];
     const double* b = Jbuf + R.pi_b[k];
@@ -1329,6 +1358,11 @@ __device__ __forceinline__ void rhs_body(RhsView R, const double* const* __restr
 #pragma unroll
         for (int c = 0; c < 3; ++c) g[c] += A[r * 3 + c] * b[r];
     }
+  }
+  if (MODE == 2) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) glane[(6 * a + c) * 64 + lane] = g[c];
+    return;
   }
   for (int k = R.pe_ptr[a] + lane; k < R.pe_ptr[a + 1]; k += 64) {
     const int e = R.pe_edge[k];
@@ -1350,25 +1384,42 @@ __device__ __forceinline__ void rhs_body(RhsView R, const double* const* __restr
 }
 __global__ __launch_bounds__(256) void k_rhs(RhsView R, const double* const* __restrict__ Jpp, const double* __restrict__ Z,
                                              const double* __restrict__ uq, double* __restrict__ gc) {
-  rhs_body(R, Jpp, Z, uq, gc, (int)blockIdx.x);
+  rhs_body<0>(R, *Jpp, Z, uq, gc, (int)blockIdx.x);
 }
 // k_assemble_chunks and k_rhs in ONE launch (both only read Z / u / the records): the first gridDim - n_asm workgroups form the reduced
 // gradient, the other n_asm assemble - the two kernels are latency bound and used to run one after the other on the solve's critical path
-// 8 waves per SIMD (64 VGPRs, 5 spilled): the launch is a latency-bound gather, what it needs is waves in flight - 267 -> 239 us for the
+// 8 waves per SIMD (64 VGPRs; 5 spilled in k_assemble_rhs<false>, which holds the direct branch too, 1 in k_assemble_rhs<true>): the launch is a latency-bound gather, what it needs is waves in flight - 267 -> 239 us for the
 // assembly phase and 1.62 -> 1.58 ms per LM iteration against the 5 waves the unconstrained 70 VGPRs gave (same idea measured on k_edge_z and
 // k_trial_errors_fused: their spills cost more than the extra waves bring)
 // (the staging LDS of the Schur pairs, 4 x 288 ASM_STAGE bytes per workgroup, allows 8 / 4 / 2 workgroups per CU at ASM_STAGE 16 / 32 / 64)
 #ifndef ASM_WAVES
 #define ASM_WAVES (ASM_STAGE <= 16 ? 8 : ASM_STAGE <= 32 ? 4 : 2)
 #endif
+// ONCE: what needs the records alone - the direct chunks, the factor loop of the gradient - was computed when they were written
+// (k_assemble_direct) and sits in the linearisation's cache Jpp[1] = [36 per direct chunk | goff: 6 x 64 lane sums per pose]; this launch,
+// which every lambda candidate repeats, then walks the Schur-pair chunks and the gradient's edge loop only (64 VGPRs, 1 spilled;
+// config 2: 86 -> 49 us per candidate, k_assemble_direct 47 us per linearisation, profiles/r08_kernel_stats.txt)
+template <bool ONCE>
 __global__ __launch_bounds__(256, ASM_WAVES) void k_assemble_rhs(AssembleView A, RhsView R, const double* const* __restrict__ Jpp, const double* __restrict__ Z,
-                                                      const double* __restrict__ uq, double* __restrict__ partial, double* __restrict__ gc, int n_asm) {
+                                                      const double* __restrict__ uq, double* __restrict__ partial, double* __restrict__ gc, int n_asm, int64_t goff) {
   // the gradient workgroups go first: a camera pose walks ~500 edges in one wave, the longest task of the launch (measured: 272 -> 270 us
   // for the assembly phase against dispatching them behind the ~8 k assembly workgroups).  n_rhs is a multiple of 8: the assembly keeps
   // its XCD mapping.
   const int n_rhs = (int)gridDim.x - n_asm;
-  if ((int)blockIdx.x < n_rhs) rhs_body(R, Jpp, Z, uq, gc, (int)blockIdx.x);
-  else asm_chunks_body(A, Jpp, Z, partial, (int)blockIdx.x - n_rhs, n_asm);
+  if (ONCE) {
+    if ((int)blockIdx.x < n_rhs) rhs_body<1>(R, nullptr, Z, uq, gc, (int)blockIdx.x, nullptr, Jpp[1] + goff);
+    else asm_chunks_body<1>(A, nullptr, Z, partial, (int)blockIdx.x - n_rhs, n_asm);
+  } else {
+    if ((int)blockIdx.x < n_rhs) rhs_body<0>(R, *Jpp, Z, uq, gc, (int)blockIdx.x);
+    else asm_chunks_body<0>(A, *Jpp, Z, partial, (int)blockIdx.x - n_rhs, n_asm);
+  }
+}
+// once per linearisation, behind the kernels that write its records: the first n_rhs workgroups (a multiple of 8) run the gradient's factor
+// loop, the other n_asm the direct chunks, one contiguous eighth of A.dch per XCD
+__global__ __launch_bounds__(256) void k_assemble_direct(AssembleView A, RhsView R, const double* __restrict__ Jbuf, double* __restrict__ cache, int n_asm, int64_t goff) {
+  const int n_rhs = (int)gridDim.x - n_asm;
+  if ((int)blockIdx.x < n_rhs) rhs_body<2>(R, Jbuf, nullptr, nullptr, nullptr, (int)blockIdx.x, cache + goff);
+  else asm_chunks_body<2>(A, Jbuf, nullptr, cache, (int)blockIdx.x - n_rhs, n_asm);
 }
 
 // scatter g' (and, multi-GPU, the damping) into the rhs tile row / diagonal
