@@ -59,14 +59,12 @@ __global__ __launch_bounds__(FUSE_THREADS) void k_ref_u(FusedBlocks F, const dou
 }
 
 // ---- points: four lanes per point, partial sums met in a fixed butterfly (k_point's mapping) ----
-__global__ void k_ref_points(PointView P, const double* const* __restrict__ Jpp, const double* __restrict__ U, const double* __restrict__ lambda_p,
-                             const double* __restrict__ dpoint, const double* __restrict__ Cq, double* __restrict__ r_point, double* __restrict__ uq) {
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t q = gid >> 2;
-  const int jl = (int)(gid & 3);
-  if (q >= P.n_point || (P.chained && P.chained[q])) return;
-  const double* __restrict__ Jbuf = *Jpp;
-  double g[3] = {0.0, 0.0, 0.0}, h[3] = {0.0, 0.0, 0.0};
+// g = sum_f Jp_f^T u_f and h = diag(sum_f Jp_f^T Jp_f) over the incidence list of point q, u_f read at the b offsets of a buffer shaped like
+// the records (the records themselves: u = b, the gradient - dogleg.h); lane jl of the point's four, every lane returns the sums
+__device__ __forceinline__ void ref_point_gather(const PointView& P, int64_t q, int jl, const double* __restrict__ Jbuf, const double* __restrict__ U,
+                                                 double g[3], double h[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) g[c] = h[c] = 0.0;
   for (int k = P.pf_ptr[q] + jl; k < P.pf_ptr[q + 1]; k += 4) {
     const double* J = Jbuf + P.pf_joff[k];
     const double* u = U + P.pf_boff[k];
@@ -77,6 +75,15 @@ __global__ void k_ref_points(PointView P, const double* const* __restrict__ Jpp,
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) { g[c] = quad_sum(g[c]); h[c] = quad_sum(h[c]); }
+}
+__global__ void k_ref_points(PointView P, const double* const* __restrict__ Jpp, const double* __restrict__ U, const double* __restrict__ lambda_p,
+                             const double* __restrict__ dpoint, const double* __restrict__ Cq, double* __restrict__ r_point, double* __restrict__ uq) {
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t q = gid >> 2;
+  const int jl = (int)(gid & 3);
+  if (q >= P.n_point || (P.chained && P.chained[q])) return;
+  double g[3], h[3];
+  ref_point_gather(P, q, jl, *Jpp, U, g, h);
   if (jl) return;
   const double lambda = lambda_p[0];
   const bool ddamp = lambda_p[1] != 0.0;
@@ -92,6 +99,25 @@ __global__ void k_ref_points(PointView P, const double* const* __restrict__ Jpp,
 }
 
 // ---- pose-like variables: one wavefront each, fixed lane partition + butterfly (k_rhs's mapping) ----
+// this lane's part of sum_f A_f^T u_f over the incidence list of pose-like variable p (u_f as in ref_point_gather)
+__device__ __forceinline__ void ref_pose_gather(const RhsView& R, int64_t p, int lane, const double* __restrict__ Jbuf, const double* __restrict__ U, double g[6]) {
+#pragma unroll
+  for (int c = 0; c < 6; ++c) g[c] = 0.0;
+  for (int k = R.pi_ptr[p] + lane; k < R.pi_ptr[p + 1]; k += 64) {
+    const double* A = Jbuf + R.pi_a[k];
+    const double* u = U + R.pi_b[k];
+    const int d = R.pi_d[k], w = R.pi_w[k];
+    if (w == 6) {
+      for (int r = 0; r < d; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) g[c] += A[r * 6 + c] * u[r];
+    } else {
+      for (int r = 0; r < d; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) g[c] += A[r * 3 + c] * u[r];
+    }
+  }
+}
 struct RefPoseArgs {
   const double* U;
   const double* Zp;        // pose-major copy of Z
@@ -109,21 +135,8 @@ __global__ __launch_bounds__(256) void k_ref_poses(RhsView R, const double* cons
   const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (p >= R.n_pose) return;
-  double g[6] = {0, 0, 0, 0, 0, 0}, s[6] = {0, 0, 0, 0, 0, 0};
-  for (int k = R.pi_ptr[p] + lane; k < R.pi_ptr[p + 1]; k += 64) {
-    const double* A = Jbuf + R.pi_a[k];
-    const double* u = a.U + R.pi_b[k];
-    const int d = R.pi_d[k], w = R.pi_w[k];
-    if (w == 6) {
-      for (int r = 0; r < d; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) g[c] += A[r * 6 + c] * u[r];
-    } else {
-      for (int r = 0; r < d; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) g[c] += A[r * 3 + c] * u[r];
-    }
-  }
+  double g[6], s[6] = {0, 0, 0, 0, 0, 0};
+  ref_pose_gather(R, p, lane, Jbuf, a.U, g);
   for (int k = R.pe_ptr[p] + lane; k < R.pe_ptr[p + 1]; k += 64) {
     const double* z = a.Zp + 18 * (int64_t)k;
     const double* u = a.uq + 3 * (int64_t)R.e_point[R.pe_edge[k]];
@@ -148,14 +161,19 @@ __global__ __launch_bounds__(256) void k_ref_poses(RhsView R, const double* cons
 }
 
 // ---- the dense prior: one wavefront per row, g_p - H_p delta ----
+// row i of H_p x, x gathered from a [6 per pose] vector; every lane returns the sum
+__device__ __forceinline__ double ref_prior_row(int dim, const double* __restrict__ H, const int32_t* __restrict__ pose, int i, int lane, const double* __restrict__ x) {
+  double s = 0.0;
+  for (int j = lane; j < dim; j += 64) s += H[(int64_t)i * dim + j] * x[6 * (int64_t)pose[j / 6] + j % 6];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
 __global__ __launch_bounds__(256) void k_ref_prior(int dim, const double* __restrict__ H, const int32_t* __restrict__ pose, const double* const* __restrict__ g_pp,
                                                    const int32_t* __restrict__ off, const double* __restrict__ dpose, double* __restrict__ r_pose, double* __restrict__ rhs) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (i >= dim) return;
-  double s = 0.0;
-  for (int j = lane; j < dim; j += 64) s += H[(int64_t)i * dim + j] * dpose[6 * (int64_t)pose[j / 6] + j % 6];
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  const double s = ref_prior_row(dim, H, pose, i, lane, dpose);
   if (lane) return;
   const int p = pose[i / 6], c = i % 6;
   const double v = (*g_pp)[i] - s;
