@@ -83,7 +83,7 @@ void drop_marginalized(std::vector<KBlock>& blocks, const std::vector<uint64_t>&
   for (const KBlock& b : blocks) {
     const int ar = f_arity(internal_type(b.type));
     KBlock k;
-    k.type = b.type; k.has_huber = b.has_huber; k.has_consts = b.has_consts;
+    k.type = b.type; k.loss = b.loss; k.has_huber = b.has_huber; k.has_consts = b.has_consts;
     for (int64_t i = 0; i < b.count(); ++i) {
       bool bad = false;
       for (int a = 0; a < ar; ++a) bad = bad || std::binary_search(mg.begin(), mg.end(), b.keys[i * ar + a]);

@@ -132,7 +132,7 @@ class ParallelObjectSmoothers:
         f = self.est[j].f
         if self.hooks is not None:
             r = self.hooks(j, f, own)
-            out = HandleILSResult([KeyedBlock(b.type, b.slot, np.array([[self._remap(j, int(k)) for k in row] for row in b.keys], dtype=np.uint64), b.meas, b.noise, b.huber_k, b.consts)
+            out = HandleILSResult([KeyedBlock(b.type, b.slot, np.array([[self._remap(j, int(k)) for k in row] for row in b.keys], dtype=np.uint64), b.meas, b.noise, b.huber_k, b.consts, b.loss)
                                    for b in r.pior_factors], list(r.failed_objects))
         elif chr(S.symbol_chr(own)) == "X":
             out = HandleILSResult([KeyedBlock(F_PRIOR_POSE3, np.array([0]), np.array([[self._remap(j, own)]], dtype=np.uint64), f.theta[own].reshape(1, 12).copy(),
@@ -184,7 +184,7 @@ class ParallelObjectSmoothers:
                 if vt == VAR_POINT3:
                     self.point_owner[int(key)] = j
             for b in blocks:
-                E.pending_blocks.append(KeyedBlock(b.type, b.slot, np.array([[self._remap(j, int(q)) for q in row] for row in b.keys], dtype=np.uint64), b.meas, b.noise, b.huber_k, b.consts))
+                E.pending_blocks.append(KeyedBlock(b.type, b.slot, np.array([[self._remap(j, int(q)) for q in row] for row in b.keys], dtype=np.uint64), b.meas, b.noise, b.huber_k, b.consts, b.loss))
             if not E.f.other_values_in_map:
                 E.status["status"] = OBJ_WAITING
                 E.status["n_pending_factors"] = sum(len(b.slot) for b in E.pending_blocks)

@@ -34,14 +34,15 @@ class KeyedBlock:
     noise: np.ndarray
     huber_k: Optional[np.ndarray]
     consts: Optional[np.ndarray]
+    loss: int = 0         # LOSS_* (dynosam_amd/graph.py): the m-estimator huber_k is the constant of
 
     def subset(self, mask):
         return KeyedBlock(self.type, self.slot[mask], self.keys[mask], self.meas[mask], self.noise[mask],
-                          None if self.huber_k is None else self.huber_k[mask], None if self.consts is None else self.consts[mask])
+                          None if self.huber_k is None else self.huber_k[mask], None if self.consts is None else self.consts[mask], self.loss)
 
 
 def keyed(block: FactorBlock, var_keys: np.ndarray) -> KeyedBlock:
-    return KeyedBlock(block.type, block.slot, var_keys[block.var_idx], block.meas, block.noise, block.huber_k, block.consts)
+    return KeyedBlock(block.type, block.slot, var_keys[block.var_idx], block.meas, block.noise, block.huber_k, block.consts, block.loss)
 
 
 
@@ -61,7 +62,7 @@ def pack_keyed_blocks(blocks: List[KeyedBlock]):
                     consts=None if (b.consts is None or not cd) else np.ascontiguousarray(b.consts, dtype=np.float64).reshape(-1))
         hold.append(arrs)
         k = kbs[i]
-        k.type, k.count = int(b.type), n
+        k.type, k.loss, k.count = int(b.type), int(b.loss), n
         k.keys, k.slot = dp(arrs["keys"], C.c_uint64), dp(arrs["slot"], C.c_int32)
         if md:
             k.meas = dp(arrs["meas"], C.c_double)
@@ -83,7 +84,7 @@ def unpack_keyed_blocks(n: int, blocks) -> List[KeyedBlock]:
         c = int(k.count)
         arr = lambda ptr, m, dt=np.float64: np.ctypeslib.as_array(ptr, shape=(c * m,)).astype(dt).copy() if (ptr and c * m) else np.zeros(0, dt)   # noqa: E731
         out.append(KeyedBlock(int(k.type), arr(k.slot, 1, np.int32), arr(k.keys, ar, np.uint64).reshape(c, ar), arr(k.meas, md).reshape(c, md), arr(k.noise, nd).reshape(c, nd),
-                              arr(k.huber_k, 1) if k.huber_k else None, arr(k.consts, cd).reshape(c, cd) if (k.consts and cd) else None))
+                              arr(k.huber_k, 1) if k.huber_k else None, arr(k.consts, cd).reshape(c, cd) if (k.consts and cd) else None, int(k.loss)))
     return out
 
 
@@ -93,11 +94,11 @@ def flatten(values: Dict[int, tuple], blocks: List[KeyedBlock], prior: Optional[
     vt = np.array([values[int(k)][0] for k in keys], dtype=np.uint8)
     st = np.array([values[int(k)][1] for k in keys], dtype=np.float64).reshape(len(keys), 12)
     out = []
-    by_type: Dict[int, List[KeyedBlock]] = {}
+    by_type: Dict[tuple, List[KeyedBlock]] = {}
     for b in blocks:
         if len(b.slot):
-            by_type.setdefault(b.type, []).append(b)
-    for t, bs in by_type.items():   # ONE struct-of-arrays block per factor class (each block costs a kernel launch per pass)
+            by_type.setdefault((b.type, b.loss), []).append(b)
+    for (t, loss), bs in by_type.items():   # ONE struct-of-arrays block per (factor class, loss kind) (each block costs a kernel launch per pass)
         ks = np.concatenate([b.keys for b in bs])
         idx = np.searchsorted(keys, ks)
         if (idx >= len(keys)).any() or not np.array_equal(keys[np.minimum(idx, len(keys) - 1)], ks):
@@ -107,7 +108,7 @@ def flatten(values: Dict[int, tuple], blocks: List[KeyedBlock], prior: Optional[
             hk = np.concatenate([b.huber_k if b.huber_k is not None else np.zeros(len(b.slot)) for b in bs])
         cs = None if bs[0].consts is None else np.concatenate([b.consts for b in bs])
         out.append(FactorBlock(t, np.concatenate([b.slot for b in bs]), idx, np.concatenate([b.meas for b in bs]),
-                               np.concatenate([b.noise for b in bs]), hk, cs))
+                               np.concatenate([b.noise for b in bs]), hk, cs, loss))
     return FlatGraph(keys, vt, st, out, {}, prior)
 
 

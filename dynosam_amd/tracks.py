@@ -42,6 +42,7 @@ class BackendParams:
     min_static_observations: int = 2
     min_dynamic_observations: int = 3
     prior_sigma: float = 1e-6
+    robust_loss: int = 0             # LOSS_* of the robustified factors (k_huber_3d_points is its constant); the reference: Huber
 
 
 def build_hybrid_graph(frames, X_world, observations, motions, object_poses, params: BackendParams = BackendParams()) -> FlatGraph:
@@ -152,7 +153,8 @@ def build_hybrid_graph(frames, X_world, observations, motions, object_poses, par
             continue
         blocks.append(FactorBlock(ftype, [r[0] for r in rws], np.array([[vid(*v) for v in r[1]] for r in rws]), np.array([r[2] for r in rws]),
                                   np.array([r[3] for r in rws]), np.array([r[4] for r in rws]) if any(r[4] > 0 for r in rws) else None,
-                                  np.array([r[5] for r in rws]) if rws[0][5].size else None))
+                                  np.array([r[5] for r in rws]) if rws[0][5].size else None,
+                                  params.robust_loss if any(r[4] > 0 for r in rws) else 0))
     return FlatGraph(keys[order], vtype[order], state[order], blocks, dict(frames=K, objects=len(objs), n_factors=slot))
 
 
