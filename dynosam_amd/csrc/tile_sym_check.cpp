@@ -251,6 +251,9 @@ int main(int argc, char** argv) {
   for (size_t l = 0; l + 1 < sym.flaunch.size() && l < sym.flaunch.size() / 4; ++l)
     for (int32_t t = sym.flaunch[l]; t < sym.flaunch[l + 1]; ++t) early_src += sym.ftask[t].nsrc;
   printf("max_src=%d early_src=%lld ", max_src, early_src);
+  int max_nloc = 0, max_nglob = 0;   // sources of a backward column record: beyond BWD_LOC / BWD_GLOB they go to the overflow lists
+  for (const BwdCol& c : sym.bcol) if (c.j >= 0) { max_nloc = std::max(max_nloc, (int)c.nloc); max_nglob = std::max(max_nglob, (int)c.nglob); }
+  printf("max_nloc=%d max_nglob=%d bwd_loc=%d bwd_glob=%d ", max_nloc, max_nglob, BWD_LOC, BWD_GLOB);
   printf("phases=%zu nt=%d tiles=%lld levels=%d fwd_launches=%zu fwd_tasks=%zu bwd_launches=%zu residual=%.3e %s\n", sym.phase_end.size(), nt, (long long)sym.n_tiles, sym.n_levels,
          sym.flaunch.size() - 1, sym.ftask.size(), sym.blaunch.size(), rmax / gmax, (rmax / gmax < 1e-10) ? "OK" : "FAIL");
   return (rmax / gmax < 1e-10) ? 0 : 1;

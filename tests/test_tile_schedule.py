@@ -117,3 +117,18 @@ def test_split_tasks_in_a_two_phase_schedule_leave_no_scratch_at_the_phase_bound
         assert res[0]["scratch"] == 0
         used += int(res[1]["scratch"] > 0)
     assert used >= 2
+
+
+def test_no_backward_column_reaches_the_overflow_lists(checker):
+    """k_back_group keeps BWD_LOC local and BWD_GLOB global sources in a column record and walks overflow lists (bsrc) beyond them.  The
+    rows of a column of L are ancestors of the column, one per level at most (the level rises strictly towards the parent); a backward
+    launch spans at most BWD_GROUP levels, so a column has at most BWD_GROUP - 1 sources inside its own launch and BWD_GROUP in the
+    previous one.  Checked on the column records of every schedule this file builds: as long as it holds the overflow loops never run
+    (no device case can cover them), and whoever changes the constants or the ranges so that they can run gets this failure as the
+    request for such a case."""
+    # (the backward schedule follows from the elimination tree alone: the forward knobs - row tasks, split tasks, source caps - leave it as it is)
+    for args in ((60, 5, 0, 1), (60, 5, 1, 1), (200, 14, 1, 2), (37, 3, 1, 3, 10), (5, 2, 1, 4), (1, 0, 1, 5), (120, 8, 1, 6, 5), (90, 6, 1, 7, 0, 20),
+                 (1200, 84, 1, 7, 0, 560), (660, 3, 2, 5, 0, 10), (660, 3, 2, 2, 20, 10), (1320, 2, 2, 9, 30, 10)):
+        r = run(checker, *args)
+        assert r["max_nloc"] <= r["bwd_loc"] and r["max_nglob"] <= r["bwd_glob"], (args, r)
+        assert r["nt"] < 4 or r["max_nloc"] + r["max_nglob"] >= 2                      # (the records are read: columns do have sources)
