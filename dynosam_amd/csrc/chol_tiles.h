@@ -11,8 +11,10 @@
 //                    diagonal targets also carry the rhs segment  r_I -= A(I,K) w_K = P' r_K
 //                    finalize the workgroup applying the LAST update to a diagonal tile inverts it straight from its
 //                             accumulators (look-ahead), see ct_spd_inverse below: only T_K^-1 is ever used
+//                    panel    (tile_sym.h panel_once) P'(I,K) of up to FWD_ROW_MAX tiles of one column stored once, for the updates
+//                             that read it one launch later with ONE contraction (pre-multiplied sources) and for the backward pass
 //   k_panel_m      w_K = T_K^-1 r_K, one small launch after the factorisation (the panel products M(I,K) = A(I,K) T_K^-1 of the
-//                  backward pass are stored by the diagonal-target updates; the kernel's panel branch serves A/B builds only)
+//                  backward pass are stored by the diagonal-target updates or by the panel tasks; the kernel's panel branch serves A/B builds only)
 //   k_back_group   backward substitution, BWD_GROUP levels per launch
 //
 // All arithmetic fp64.  Every reduction has a fixed order: results are run-to-run deterministic.
@@ -487,25 +489,52 @@ __device__ __forceinline__ void ct_run_task(const CholLevelArgs& a, const FwdTas
   const ct_d4 zero = {0.0, 0.0, 0.0, 0.0};
 #define CT_END_STAMP() do { if (dbg_all) dbg_all[1] = (long long)__builtin_readcyclecounter(); } while (0)
 
+  const int npm = t.kind >> FK_PM_SHIFT;   // pre-multiplied sources (tile_sym.h: panel_once): their product P' is read from a.L, where a panel task left it
+  if (t.kind & FK_PANEL) {
+    // up to FWD_ROW_MAX tiles (I_j, K) of one source column: P'(I_j,K) = A(I_j,K) T_K^-1 to the panel buffer, T_K^-1 staged once; the tiles alternate
+    // between two LDS buffers (one barrier per tile), tile j + 1 is fetched while tile j is computed (unconditional loads, clamped index)
+    const int n = t.nsrc;
+    ct_t2 va = ct_gld(a.A + (int64_t)t.ai0 * CT_TT, tid);
+    const ct_t2 vl = ct_gld(a.Tinv + (int64_t)t.k0 * CT_TT, tid);
+    FwdSrc nx = a.src[t.src0 + min(1, n - 1)];
+    int cur = t.ai0;
+    ct_lst(LI, tid, vl);
+    for (int i = 0;; ++i) {
+      double* const buf = (i & 1) ? XB : XA;
+      ct_lst(buf, tid, va);
+      const FwdSrc nx2 = a.src[t.src0 + min(i + 2, n - 1)];
+      va = ct_gld(a.A + (int64_t)nx.ai * CT_TT, tid);
+      __syncthreads();                   // (the buffer's previous tile, i - 2, was consumed in front of the barrier of tile i - 1)
+      const ct_d4 p = ct_mma_abt<false>(buf, LI, bi, bj, lane, zero);
+      ct_gstore_frag(a.L + (int64_t)cur * CT_TT, bi, bj, lane, p);
+      if (i + 1 >= n) break;
+      cur = nx.ai;
+      nx = nx2;
+    }
+    CT_END_STAMP();
+    return;
+  }
   if (t.kind & FK_ROW) {
     // up to FWD_ROW_MAX off-diagonal targets (I, I_j) of one tile row and one source column K: P' = A(I,K) T_K^-1 is formed
     // once, every target then costs ONE contraction with the raw column operand, A(I,I_j) -= P' A(I_j,K)^T; the column
     // operands alternate between two LDS tiles (one barrier per target) and the operand and target of item j + 1 are fetched
-    // while item j is computed
+    // while item j is computed.  Pre-multiplied (npm): P' itself is staged from the panel buffer - no T^-1, no contraction, one barrier.
     const int n = t.nsrc;
-    const ct_t2 va = ct_gld(a.A + (int64_t)t.ai0 * CT_TT, tid), vb = ct_gld(a.A + (int64_t)t.aj0 * CT_TT, tid), vl = ct_gld(a.Tinv + (int64_t)t.k0 * CT_TT, tid);
+    const ct_t2 va = ct_gld((npm ? a.L : a.A) + (int64_t)t.ai0 * CT_TT, tid), vb = ct_gld(a.A + (int64_t)t.aj0 * CT_TT, tid), vl = ct_gld(a.Tinv + (int64_t)t.k0 * CT_TT, tid);
     ct_d4 acc = ct_gload_frag(a.A + (int64_t)t.tgt * CT_TT, bi, bj, lane), accn = zero;
     FwdSrc nx = a.src[t.src0 + 1];
     ct_t2 vbn = ct_gld(a.A + (int64_t)nx.aj * CT_TT, tid);
     accn = ct_gload_frag(a.A + (int64_t)nx.ai * CT_TT, bi, bj, lane);
     ct_lst(XA, tid, va);
     ct_lst(XB, tid, vb);
-    ct_lst(LI, tid, vl);
+    if (!npm) ct_lst(LI, tid, vl);
     __syncthreads();
-    const ct_d4 p = ct_mma_abt<false>(XA, LI, bi, bj, lane, zero);   // T^-1 is symmetric
-    __syncthreads();
-    ct_store_frag(XA, bi, bj, lane, p);
-    __syncthreads();                     // P' published; LI is free from here on
+    if (!npm) {
+      const ct_d4 p = ct_mma_abt<false>(XA, LI, bi, bj, lane, zero);   // T^-1 is symmetric
+      __syncthreads();
+      ct_store_frag(XA, bi, bj, lane, p);
+      __syncthreads();                   // P' published; LI is free from here on
+    }
     int cur = t.tgt;
     double pa[8];
     ct_load_neg_afrag(XA, bi, lane, pa);
@@ -566,12 +595,15 @@ __device__ __forceinline__ void ct_run_task(const CholLevelArgs& a, const FwdTas
     // Every load of the loop is UNCONDITIONAL (clamped index; a diagonal target fetches its operand twice, every lane fetches
     // an r_K element): with loads under a condition the compiler waits for ALL outstanding loads before it touches any of
     // them (vmcnt(0)), which turned the prefetch back into two dependent memory round trips per source.
+    // A pre-multiplied source (the first npm) stages P'(I,K) from the panel buffer in place of T_K^-1 and the column operand in place of A(I,K) (a diagonal
+    // target's column operand IS A(I,K)): the same three loads through other pointers, then ONE contraction and two barriers instead of four.
     const int ns = t.nsrc;
     FwdSrc s{t.ai0, t.aj0, t.k0};        // the first source rides in the task record (one dependent load less on the critical path)
     FwdSrc sn = a.src[t.src0 + min(1, ns - 1)];
     // P' = A(I,K) T_K^-1, then A(I,I') -= P' A(I',K)^T with the raw column operand (I' = I for a diagonal target, of which
     // only the lower triangle is ever read): two contractions per source
-    ct_t2 va = ct_gld(a.A + (int64_t)s.ai * CT_TT, tid), vb = ct_gld(a.A + (int64_t)s.aj * CT_TT, tid), vl = ct_gld(a.Tinv + (int64_t)s.k * CT_TT, tid);
+    ct_t2 va = ct_gld(a.A + (int64_t)(npm > 0 ? s.aj : s.ai) * CT_TT, tid), vb = ct_gld(a.A + (int64_t)s.aj * CT_TT, tid);
+    ct_t2 vl = ct_gld(npm > 0 ? a.L + (int64_t)s.ai * CT_TT : a.Tinv + (int64_t)s.k * CT_TT, tid);
     double wv = *(a.Y + s.k * CT_TS + (tid & 31));
     for (int q = 0; q < ns; ++q) {
       if (q) {
@@ -584,19 +616,22 @@ __device__ __forceinline__ void ct_run_task(const CholLevelArgs& a, const FwdTas
       if (diag && tid < CT_TS) S.wk[tid] = wv;
       // next source (or, at the end, the last one again)
       const FwdSrc sn2 = a.src[t.src0 + min(q + 2, ns - 1)];
-      va = ct_gld(a.A + (int64_t)sn.ai * CT_TT, tid);
+      const bool pm_next = q + 1 < npm;
+      va = ct_gld(a.A + (int64_t)(pm_next ? sn.aj : sn.ai) * CT_TT, tid);
       vb = ct_gld(a.A + (int64_t)sn.aj * CT_TT, tid);
-      vl = ct_gld(a.Tinv + (int64_t)sn.k * CT_TT, tid);
+      vl = ct_gld(pm_next ? a.L + (int64_t)sn.ai * CT_TT : a.Tinv + (int64_t)sn.k * CT_TT, tid);
       wv = *(a.Y + sn.k * CT_TS + (tid & 31));
       const int32_t cur_ai = s.ai;
       s = sn; sn = sn2;
       __syncthreads();
       if (q == 0) CT_STAMP(1);
-      const ct_d4 p = ct_mma_abt<false>(XA, LI, bi, bj, lane, zero);   // T^-1 is stored exactly symmetric
-      if (diag) ct_gstore_frag(a.L + (int64_t)cur_ai * CT_TT, bi, bj, lane, p);
-      __syncthreads();                   // every wave has finished LI
-      ct_store_frag(LI, bi, bj, lane, p);
-      __syncthreads();
+      if (q >= npm) {
+        const ct_d4 p = ct_mma_abt<false>(XA, LI, bi, bj, lane, zero);   // T^-1 is stored exactly symmetric
+        if (diag) ct_gstore_frag(a.L + (int64_t)cur_ai * CT_TT, bi, bj, lane, p);
+        __syncthreads();                 // every wave has finished LI
+        ct_store_frag(LI, bi, bj, lane, p);
+        __syncthreads();
+      }
       acc = ct_mma_abt<true>(LI, diag ? XA : XB, bi, bj, lane, acc);
       if (diag) {
         const int i = tid & 31, kg = tid >> 5;
@@ -686,7 +721,7 @@ __device__ __forceinline__ void ct_level_body(const CholLevelArgs& a, int task0,
       dbg_all = a.dbg + a.dbg[16 * lvl + 14] + 4 * blockIdx.x;
       dbg_all[0] = (long long)__builtin_readcyclecounter();
       dbg_all[2] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-      dbg_all[3] = (long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) | ((long long)t.kind << 8) | ((long long)t.nsrc << 16);
+      dbg_all[3] = (long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) | ((long long)(t.kind & 0xff) << 8) | ((long long)t.nsrc << 16);
     }
   }
 #if CT_FINAL_PRIO

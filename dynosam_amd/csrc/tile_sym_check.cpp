@@ -3,6 +3,7 @@
 // forward/backward task lists exactly as the HIP kernels of chol_tiles.h consume them (tasks of
 // one launch in shuffled order, to prove they are independent) and compares the solution with a
 // dense Cholesky solve.   usage: tile_sym_check <n_pose> <bandwidth_in_poses> <mode> <seed> [extra_links] [split]
+// (mode 0: band, 1: twisted band, 2: star of chains, 3: the star in a two-window nested-dissection order)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +53,31 @@ int main(int argc, char** argv) {
   // order
   const int split = argc > 6 ? atoi(argv[6]) : np / 2;
   PoseLayout lay = make_layout(np, mode == 1 ? split : np, TS);
+  if (mode == 3) {
+    // the star of mode 2 in the order of the solver's single-GPU nested dissection (make_layout_nd with two windows): `split` object chains and the hub (camera)
+    // chain of np / (split + 1) frames each; per chain the two windows are eliminated from both ends towards their middle, object chains first, and the
+    // 14-frame separator of every chain last - the shape of the benchmark graph's schedule (wide launches in front, a dense separator tail; with the band-wide
+    // coupling below 4 101 tiles, 13 821 tasks and up to ten sources per target, where the benchmark graph has 4 456, 14 743 and ten)
+    const int nc = std::max(1, split), F = np / (nc + 1), sw = std::min(14, F / 4), s0 = F / 2 - sw / 2, s1 = s0 + sw;
+    std::vector<std::vector<int32_t>> segs;
+    for (int c = 0; c <= nc; ++c)
+      for (int wdw = 0; wdw < 2; ++wdw) {
+        const int lo = wdw ? s1 : 0, hi = wdw ? F : s0, mid = lo + (hi - lo) / 2;
+        std::vector<int32_t> a, b;
+        for (int u = lo; u < mid; ++u) a.push_back(c * F + u);
+        for (int u = hi - 1; u >= mid; --u) b.push_back(c * F + u);
+        segs.push_back(a); segs.push_back(b);
+      }
+    for (int c = 0; c <= nc; ++c) {
+      std::vector<int32_t> sv;
+      for (int u = s0; u < s1; ++u) sv.push_back(c * F + u);
+      segs.push_back(sv);
+    }
+    std::vector<int32_t> rest;
+    for (int u = (nc + 1) * F; u < np; ++u) rest.push_back(u);
+    if (!rest.empty()) segs.push_back(rest);
+    lay = make_layout_segments(np, segs, TS);
+  }
   const int n = lay.n_scalar, nt = (n + TS - 1) / TS, npad = nt * TS;
   std::vector<char> is_pad(npad, 0);
   for (int i : lay.pad) is_pad[i] = 1;
@@ -72,7 +98,7 @@ int main(int argc, char** argv) {
         lower.push_back({hi / TS, lo / TS});
       }
   };
-  if (mode == 2) {
+  if (mode == 2 || mode == 3) {
     // a star of chains, chains first: `split` chains of equal length, each a band of width bwp, every pose k of a chain also coupled with
     // poses k - 1, k of the hub chain (the last one) - the shape of a chains-first elimination order (object chains, camera chain last):
     // the tiles of the hub block collect one update per chain and level
@@ -81,6 +107,9 @@ int main(int argc, char** argv) {
       for (int k = 0; k < len; ++k) {
         const int a = c * len + k;
         for (int b = std::max(c * len, a - bwp); b <= a; ++b) link(a, b);
+        if (c < nc && mode == 3) {   // a tracked object point ties every object pose of its track to every camera pose of it: the hub frames of the whole band, both sides
+          for (int j = std::max(0, k - bwp); j <= std::min(len - 1, k + bwp); ++j) link(nc * len + j, a);
+        } else
         if (c < nc) { link(nc * len + k, a); if (k) link(nc * len + k - 1, a); }
       }
     for (int a = (nc + 1) * len; a < np; ++a) link(a, a);
@@ -98,9 +127,37 @@ int main(int argc, char** argv) {
   if (getenv("TS_BITMAP_MAX")) sym.bitmap_max_nt = atoi(getenv("TS_BITMAP_MAX"));   // 0: the sort path of very large systems
   if (getenv("TS_SPLIT")) sym.split_max = atoi(getenv("TS_SPLIT"));   // several workgroups per target with many sources (scratch tiles)
   if (getenv("TS_SRC_CAP")) sym.src_cap = atoi(getenv("TS_SRC_CAP"));   // sources a target takes per launch (0: all behind their columns)
+  if (getenv("TS_PANEL_ONCE")) sym.panel_once = atoi(getenv("TS_PANEL_ONCE")) != 0;   // panel tiles formed once, pre-multiplied sources (off unless asked for)
+  if (getenv("TS_PANEL_MIN")) sym.panel_min_tasks = atoi(getenv("TS_PANEL_MIN"));
+  if (getenv("TS_PANEL_SLACK")) sym.panel_slack = atoi(getenv("TS_PANEL_SLACK"));
   const int nel = getenv("TS_NELIM") ? atoi(getenv("TS_NELIM")) : -1;   // two-phase schedule: must still solve the whole system
   if (getenv("TS_SPLIT") == nullptr) sym.split_max = 0;   // (the un-split schedule unless asked for)
-  sym.analyse(nt, lower, true, nel < 0 ? -1 : std::min(nel, nt), nel >= 0);
+  const bool partial = nel >= 0 && getenv("TS_PARTIAL") && atoi(getenv("TS_PARTIAL"));   // the first phase alone (marginalisation): the schedule is printed, not executed
+  sym.analyse(nt, lower, true, nel < 0 ? -1 : std::min(nel, nt), nel >= 0 && !partial);
+  // the forward schedule in one number (FNV-1a over the task records, the sources and the launch ranges), and what the panel_once option made of it
+  auto schedule_tokens = [&]() {
+    uint64_t h = 1469598103934665603ull;
+    auto eat = [&](const void* p, size_t n) { for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char*)p)[i]) * 1099511628211ull; };
+    eat(sym.ftask.data(), sym.ftask.size() * sizeof(FwdTask)); eat(sym.fsrc.data(), sym.fsrc.size() * sizeof(FwdSrc)); eat(sym.flaunch.data(), sym.flaunch.size() * sizeof(int32_t));
+    long long pm_all = 0, pm_mixed = 0, pm_diag = 0, pm_split = 0, pm_rows = 0, panel_one = 0, panel_full = 0, cols_plain = 0;
+    std::vector<char> has_panel(nt, 0);
+    for (const FwdTask& t : sym.ftask) {
+      const int pm = t.kind >> FK_PM_SHIFT;
+      if (t.kind & FK_PANEL) { has_panel[t.k0] = 1; panel_one += t.nsrc == 1; panel_full += t.nsrc == FWD_ROW_MAX; continue; }
+      if (!pm) continue;
+      if (t.kind & FK_ROW) { ++pm_rows; continue; }
+      pm_all += pm == t.nsrc; pm_mixed += pm < t.nsrc; pm_diag += (t.kind & FK_DIAG) != 0; pm_split += t.tgt >= sym.n_tiles || t.add0 != 0;
+    }
+    for (int K = 0; K < nt; ++K) cols_plain += !has_panel[K] && sym.col_ptr[K + 1] - sym.col_ptr[K] > 1;
+    printf("contractions=%lld panel_tasks=%lld premul_sources=%lld inline_sources=%lld ", (long long)sym.fwd_counts[0], (long long)sym.fwd_counts[1], (long long)sym.fwd_counts[2], (long long)sym.fwd_counts[3]);
+    printf("pm_all=%lld pm_mixed=%lld pm_diag=%lld pm_split=%lld pm_rows=%lld panel_one=%lld panel_full=%lld cols_plain=%lld ", pm_all, pm_mixed, pm_diag, pm_split, pm_rows, panel_one, panel_full, cols_plain);
+    printf("fwd_sources=%zu sched_hash=%llu ", sym.fsrc.size(), (unsigned long long)(h >> 12));
+  };
+  if (partial) {
+    schedule_tokens();
+    printf("scratch=%d phases=%zu nt=%d tiles=%lld levels=%d fwd_launches=%zu fwd_tasks=%zu\n", sym.n_scratch, sym.phase_end.size(), nt, (long long)sym.n_tiles, sym.n_levels, sym.flaunch.size() - 1, sym.ftask.size());
+    return 0;
+  }
   // tile buffers
   std::vector<double> A(((size_t)sym.n_tiles + sym.n_scratch) * TT, 0.0), L((size_t)sym.n_tiles * TT, 0.0), Li((size_t)nt * TT), r(g), y(npad), w(npad), s(npad, 0.0), x(npad);
   r.resize((size_t)npad + (size_t)sym.n_scratch * TS, 0.0);   // scratch rhs segments of split tasks: columns nt ...
@@ -114,6 +171,30 @@ int main(int argc, char** argv) {
   for (auto& ij : lower)
     if (sym.find(ij.first, ij.second) < 0) { printf("FAIL: tile (%d,%d) missing\n", ij.first, ij.second); return 1; }
   std::vector<double> P(TT), Q(TT), tmp(TS);
+  // the panel buffer of the kernels (CholLevelArgs::L): P'(I,K) = A(I,K) T_K^-1, stored by the diagonal target's inline source or by a panel task - exactly
+  // once - and read by pre-multiplied sources one launch later.  Poisoned: a read of a tile that was not stored in an EARLIER launch fails.
+  std::vector<double> Pm((size_t)sym.n_tiles * TT, std::nan("")), Ti(TT), rk(npad, 0.0);
+  std::vector<int32_t> pm_launch((size_t)sym.n_tiles, -1);
+  auto tinv = [&](int K) {   // T_K^-1 = Linv^T Linv
+    const double* li = &Li[(size_t)K * TT];
+    for (int i = 0; i < TS; ++i)
+      for (int j = 0; j < TS; ++j) { double acc = 0; for (int k = 0; k < TS; ++k) acc += li[k + TS * i] * li[k + TS * j]; Ti[i + TS * j] = acc; }
+  };
+  auto store_pm = [&](int32_t tile, int K, int launch) {
+    if (pm_launch[tile] >= 0) { printf("FAIL: panel tile %d stored twice\n", tile); return false; }
+    tinv(K);
+    mul_abt(&A[(size_t)tile * TT], Ti.data(), &Pm[(size_t)tile * TT]);   // (T^-1 is symmetric)
+    pm_launch[tile] = launch;
+    return true;
+  };
+  auto read_pm = [&](int32_t tile, int launch) {
+    if (pm_launch[tile] < 0 || pm_launch[tile] >= launch) { printf("FAIL: pre-multiplied source reads panel tile %d before it is stored\n", tile); return false; }
+    return true;
+  };
+  auto sub_pbt = [&](const double* Pp, const double* B, double* Tg) {   // Tg -= Pp B^T
+    for (int i = 0; i < TS; ++i)
+      for (int j = 0; j < TS; ++j) { double acc = 0; for (int k = 0; k < TS; ++k) acc += Pp[i + TS * k] * B[j + TS * k]; Tg[i + TS * j] -= acc; }
+  };
   // ---- forward ----
   for (size_t l = 0; l + 1 < sym.flaunch.size(); ++l) {
     // where the phases of a sharded schedule meet (the all-reduce over [tiles | scratch tiles | rhs]) every scratch tile must be zero again
@@ -127,6 +208,22 @@ int main(int argc, char** argv) {
     for (int32_t id : ids) {
       const FwdTask& t = sym.ftask[id];
 
+      const int npm = t.kind >> FK_PM_SHIFT;
+      if (t.kind & FK_PANEL) {   // panel tiles of one column
+        if (t.nsrc < 1 || t.nsrc > FWD_ROW_MAX || sym.fsrc[t.src0].ai != t.ai0) { printf("FAIL: malformed panel task\n"); return 1; }
+        for (int g = 0; g < t.nsrc; ++g) {
+          const FwdSrc& it = sym.fsrc[t.src0 + g];
+          if (it.k != t.k0 || it.ai < sym.col_ptr[it.k] + 1 || it.ai >= sym.col_ptr[it.k + 1]) { printf("FAIL: panel tile outside its column\n"); return 1; }
+          if (!store_pm(it.ai, it.k, (int)l)) return 1;
+        }
+        continue;
+      }
+      if ((t.kind & FK_ROW) && npm) {   // ... sharing a stored product
+        if (sym.fsrc[t.src0].ai != t.tgt || sym.fsrc[t.src0].aj != t.aj0 || t.nsrc < 2 || t.nsrc > FWD_ROW_MAX) { printf("FAIL: malformed row task\n"); return 1; }
+        if (!read_pm(t.ai0, (int)l)) return 1;
+        for (int g = 0; g < t.nsrc; ++g) sub_pbt(&Pm[(size_t)t.ai0 * TT], &A[(size_t)sym.fsrc[t.src0 + g].aj * TT], &A[(size_t)sym.fsrc[t.src0 + g].ai * TT]);
+        continue;
+      }
       if (t.kind & FK_ROW) {   // several targets of one tile row sharing P = A(ai0) Linv^T
         mul_abt(&A[(size_t)t.ai0 * TT], &Li[(size_t)t.k0 * TT], P.data());
         if (sym.fsrc[t.src0].ai != t.tgt || sym.fsrc[t.src0].aj != t.aj0 || t.nsrc < 2 || t.nsrc > FWD_ROW_MAX) { printf("FAIL: malformed row task\n"); return 1; }
@@ -156,6 +253,16 @@ int main(int argc, char** argv) {
       }
       for (int32_t q = t.src0; q < t.src0 + t.nsrc; ++q) {
         const FwdSrc& sc = sym.fsrc[q];
+        if (q - t.src0 < npm) {   // pre-multiplied: one contraction with the stored product, the rhs from it and r_K
+          if (t.kind & FK_FINAL) { printf("FAIL: a finalising task has a pre-multiplied source\n"); return 1; }
+          if (!read_pm(sc.ai, (int)l)) return 1;
+          const double* Pp = &Pm[(size_t)sc.ai * TT];
+          sub_pbt(Pp, &A[(size_t)sc.aj * TT], T);
+          if (t.kind & FK_DIAG)
+            for (int i = 0; i < TS; ++i) { double acc = 0; for (int k = 0; k < TS; ++k) acc += Pp[i + TS * k] * rk[sc.k * TS + k]; r[t.col * TS + i] -= acc; }
+          continue;
+        }
+        if ((t.kind & FK_DIAG) && sc.ai >= sym.col_ptr[sc.k] + 1 && !store_pm(sc.ai, sc.k, (int)l)) return 1;   // (the kernel stores P' of a diagonal target's inline source)
         mul_abt(&A[(size_t)sc.ai * TT], &Li[(size_t)sc.k * TT], P.data());
         mul_abt(&A[(size_t)sc.aj * TT], &Li[(size_t)sc.k * TT], Q.data());
         for (int i = 0; i < TS; ++i)
@@ -176,11 +283,15 @@ int main(int argc, char** argv) {
       if (t.kind & FK_FINAL) {
         potrf_inv(T, &L[(size_t)t.tgt * TT], &Li[(size_t)t.col * TT]);
         const double* li = &Li[(size_t)t.col * TT];
+        for (int i = 0; i < TS; ++i) rk[t.col * TS + i] = r[t.col * TS + i];   // (CholLevelArgs::Y)
         for (int i = 0; i < TS; ++i) { double acc = 0; for (int k = 0; k <= i; ++k) acc += li[i + TS * k] * r[t.col * TS + k]; y[t.col * TS + i] = acc; }
         for (int c = 0; c < TS; ++c) { double acc = 0; for (int k = c; k < TS; ++k) acc += li[k + TS * c] * y[t.col * TS + k]; w[t.col * TS + c] = acc; }
       }
     }
   }
+  // every panel tile of an eliminated column was stored (exactly once: store_pm): the backward pass, the refinement and the covariances read whole panels
+  for (const PanelTask& pt : sym.panel)
+    if (pt.tile >= 0 && pm_launch[pt.tile] < 0) { printf("FAIL: panel tile %d was never stored\n", pt.tile); return 1; }
   // ---- panels: M(I,K) = (A Linv^T) Linv ----
   for (const PanelTask& pt : sym.panel) {
     if (pt.tile < 0) continue;
@@ -251,6 +362,7 @@ int main(int argc, char** argv) {
   for (size_t l = 0; l + 1 < sym.flaunch.size() && l < sym.flaunch.size() / 4; ++l)
     for (int32_t t = sym.flaunch[l]; t < sym.flaunch[l + 1]; ++t) early_src += sym.ftask[t].nsrc;
   printf("max_src=%d early_src=%lld ", max_src, early_src);
+  schedule_tokens();
   int max_nloc = 0, max_nglob = 0;   // sources of a backward column record: beyond BWD_LOC / BWD_GLOB they go to the overflow lists
   for (const BwdCol& c : sym.bcol) if (c.j >= 0) { max_nloc = std::max(max_nloc, (int)c.nloc); max_nglob = std::max(max_nglob, (int)c.nglob); }
   printf("max_nloc=%d max_nglob=%d bwd_loc=%d bwd_glob=%d ", max_nloc, max_nglob, BWD_LOC, BWD_GLOB);
