@@ -35,6 +35,9 @@ Structures (graph(name), built with G.FlatGraph directly; every pose-like variab
 stay far below 1e-9):
     degree        nine cameras; PoseToPoint points seen from 1, 2, 3, 4, 5, 7, 8 and 9 of them (three each), stereo points, one object with
                   HybridMotion / StereoHybridMotion points and HybridSmoothing
+    degree_wide   thirteen cameras; PoseToPoint points seen from 1, 7, 8, 9, 11, 12 and 13 of them (two each), one object with HybridMotion
+                  points of 1, 2, 4 and 6 factors (for the covariance queries, tests/marginal_reference.py: a point's edge count e gives
+                  e^2 pairs to 64 lanes)
     pairs_P       two and three poses sharing P points each, P in 1, 15, 16, 17, 63, 64, 65, 129
     chain_ternary WCME: tracklets of 2, 3, 14, 15 and 40 per-frame points (LandmarkMotionTernary), two factors on one link, three extra
                   poses that see only the first, only the last and every position of a chain
@@ -425,6 +428,35 @@ def g_degree():
     return B.graph()
 
 
+WIDE_DEGREES = (1, 7, 8, 9, 11, 12, 13)
+WIDE_HYBRID = (1, 2, 4, 6)
+
+
+def g_degree_wide():
+    B = Builder(12)
+    K = 13
+    X = _cameras(B, K, prior=0.1)
+    Le = _mul(B.gt[X[0]], (synth.so3_exp(np.array([0.1, -0.2, 0.05])), np.array([1.0, -0.5, 9.0])))
+    H = [B.pose(S.ObjectMotionSymbol(1, k), _exp(k * OBJ_XI)) for k in range(K)]
+    for k in range(K):
+        B.prior(H[k], 0.1)
+        if k >= 2:
+            B.add(G.F_HYBRID_SMOOTHING, [H[k - 2], H[k - 1], H[k]], [], B.iso6(0.01, 0.1), synth.to12(Le))
+    t = 0
+    for deg in WIDE_DEGREES:                   # e edges: e^2 = 1, 49, 64, 81, 121, 144, 169 pairs for the 64 lanes of a point's wavefront
+        for _rep in range(2):
+            seen = np.sort(B.rng.choice(K, deg, replace=False))
+            l = B.point(S.StaticLandmarkSymbol(t), _front(B, X[6], (4.0, 10.0))); t += 1
+            for k in seen:
+                B.ptp(X[k], l, 0.2)
+    for deg in WIDE_HYBRID:                    # a camera and a motion edge per factor: 2, 4, 8 and 12 edges
+        m = B.point(S.HybridDynamicKey(1000 + t), B.rng.normal(0, 0.5, 3)); t += 1
+        k0 = int(B.rng.integers(0, K - deg + 1))
+        for k in range(k0, k0 + deg):
+            B.hybrid(X[k], H[k], m, Le, 0.2)
+    return B.graph()
+
+
 PAIR_COUNTS = (1, 15, 16, 17, 63, 64, 65, 129)
 
 
@@ -610,7 +642,7 @@ def g_clip():
     return B.graph(dict(clipped=(S.CameraPoseSymbol(5), S.StaticLandmarkSymbol(8))))
 
 
-STRUCTURES = {"degree": g_degree, "chain_ternary": g_chain_ternary, "chain_wcpe": g_chain_wcpe, "chain_weak": g_chain_weak,
+STRUCTURES = {"degree": g_degree, "degree_wide": g_degree_wide, "chain_ternary": g_chain_ternary, "chain_wcpe": g_chain_wcpe, "chain_weak": g_chain_weak,
               "tree_band": lambda: g_tree("band"), "tree_loops": lambda: g_tree("loops"), "tree_star": lambda: g_tree("star"),
               "kept_hybrid": g_kept_hybrid, "kept_chain": g_kept_chain, "clip": g_clip}
 STRUCTURES.update({f"pairs_{P}": functools.partial(g_pairs, P) for P in PAIR_COUNTS})
