@@ -114,7 +114,7 @@ struct LayoutInput {
   int maxd = 0;                          // widest block, in variables
   int64_t n_elim_pose = -1;              // >= 0: partial elimination of the first n_elim_pose variables (marginalisation)
   int TS = 32;
-  bool tiles = true, dense_tiles = false, multi = false;
+  bool dense_tiles = false, multi = false;
   int order_mode = 1;                    // 0 frame order, 1 twisted
   int64_t n_rp = 0;
   // sharded
@@ -383,7 +383,7 @@ inline LayoutChoice choose_layout(const LayoutInput& in, const LayoutKnobs& knob
     R.n_elim_tiles = (best.n_scalar - 6 * (int32_t)segs[1].size()) / in.TS;
   } else if (in.multi)
     best = sharded_layout(in, knobs, R.n_elim_tiles);
-  else if (in.tiles && in.order_mode == 1 && in.np >= 8 && in.n_rp == 0)
+  else if (in.order_mode == 1 && in.np >= 8 && in.n_rp == 0)
     best = single_gpu_layout(in, knobs, parallel_for, tick);
   else
     best = make_layout(in.np, in.np, in.TS);
