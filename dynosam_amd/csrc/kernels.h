@@ -1487,13 +1487,33 @@ struct PriorView {
   double c;
 };
 
+// v = Lambda_i . dx is accumulated in twice the working precision (Dot2 of Ogita, Rump and Oishi: the rounding errors of every product -
+// fma - and of every sum - Knuth's TwoSum - are collected in e; s + e is the sum).  A carried marginal is nearly singular along the
+// directions in which the next window moves its variables: an object motion re-estimated by 1 m against entries of 1e4 whose products
+// cancel to 1e-2 in every row, 0.5 dx' Lambda dx = 9e-5 of terms that sum to 4.5e3 in magnitude.  A plain fma chain leaves 5e-14 in
+// Q(dx) there - 7e-12 of the whole marginal's constant, the error tests/test_gpu_marginalize_reference.py found in a stream's second
+// window - and the same relative error in the rows of the gradient.
+__device__ __forceinline__ void dot2_add(double a, double b, double& s, double& e) {   // (s, e) += a b
+#pragma clang fp contract(off)
+  const double p = a * b, pe = fma(a, b, -p), t = s + p, z = t - s;
+  e += ((s - (t - z)) + (p - z)) + pe;
+  s = t;
+}
+__device__ __forceinline__ void sum2_add(double x, double xe, double& s, double& e) {   // (s, e) += (x, xe)
+#pragma clang fp contract(off)
+  const double t = s + x, z = t - s;
+  e += ((s - (t - z)) + (x - z)) + xe;
+  s = t;
+}
+
 __device__ __forceinline__ double prior_q(const PriorView& P, const double* __restrict__ d /*LDS*/, double* __restrict__ red /*LDS 256*/,
                                           double* __restrict__ g_out) {
   double part = 0.0;
   for (int i = threadIdx.x; i < P.dim; i += 256) {
-    double v = 0.0;
+    double v = 0.0, ve = 0.0;
     const double* row = P.Lambda + (int64_t)i * P.dim;
-    for (int j = 0; j < P.dim; ++j) v = fma(row[j], d[j], v);
+    for (int j = 0; j < P.dim; ++j) dot2_add(row[j], d[j], v, ve);
+    v += ve;
     if (g_out) g_out[i] = P.eta[i] - v;
     part += d[i] * (0.5 * v - P.eta[i]);
   }
@@ -1570,14 +1590,18 @@ __global__ __launch_bounds__(256) void k_prior_rows(PriorView P, int nvec, const
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= P.dim) return;
   const double* row = P.Lambda + (int64_t)i * P.dim;
-  double v0 = 0.0, v1 = 0.0;
+  double v0 = 0.0, v1 = 0.0, e0 = 0.0, e1 = 0.0;   // (twice the working precision: see prior_q)
   for (int j = lane; j < P.dim; j += 64) {
     const double a = row[j];
-    v0 = fma(a, d0[j], v0);
-    if (nvec > 1) v1 = fma(a, d1[j], v1);
+    dot2_add(a, d0[j], v0, e0);
+    if (nvec > 1) dot2_add(a, d1[j], v1, e1);
   }
 #pragma unroll
-  for (int m = 32; m > 0; m >>= 1) { v0 += __shfl_xor(v0, m, 64); v1 += __shfl_xor(v1, m, 64); }
+  for (int m = 32; m > 0; m >>= 1) {
+    const double o0 = __shfl_xor(v0, m, 64), oe0 = __shfl_xor(e0, m, 64), o1 = __shfl_xor(v1, m, 64), oe1 = __shfl_xor(e1, m, 64);
+    sum2_add(o0, oe0, v0, e0); sum2_add(o1, oe1, v1, e1);
+  }
+  v0 += e0; v1 += e1;
   if (lane == 0) {
     if (g_out) g_out[i] = P.eta[i] - v0;
     rowq[i] = d0[i] * (0.5 * v0 - P.eta[i]);
