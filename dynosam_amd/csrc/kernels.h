@@ -898,8 +898,7 @@ __global__ void k_chain_factor(ChainView V, PointView P, const double* const* __
 // first..last of the edge as consecutive "sub-edges", so that assembly / rhs / back-substitution see a chain edge as
 // a run of ordinary pose-point edges:  W H_gg^-1 W'^T = sum_i Z_i Z'_i^T.
 // A pose-like neighbour of an eliminated point is a pose (Jacobian block 3x6) or a Point3 KEPT in the reduced system (a 6-wide
-// pseudo-pose whose block is 3x3: columns 3..5 are zero).  The width rides in bit 62 of the block's offset.
-constexpr int64_t JC_W3 = 1ll << 62;
+// pseudo-pose whose block is 3x3: columns 3..5 are zero).  The width rides in bit 62 of the block's offset (JC_W3, factor_traits.h).
 __device__ __forceinline__ void load_jc(const double* __restrict__ Jbuf, int64_t jc, double* __restrict__ out /*18: 3x6 row-major*/) {
   if (jc & JC_W3) {
     const double* p = Jbuf + (jc & ~JC_W3);

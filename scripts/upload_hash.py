@@ -53,6 +53,14 @@ c = upload(g)
 c.marginalize([int(k) for k, f in zip(g.var_keys, g.meta["var_frame"]) if f < 4])
 c.close()
 
+# the graph the next window starts from (tests/test_gpu_window.py): linear containers and the dense prior a marginalisation left, on
+# poses and on points kept in the reduced system
+import test_gpu_window as TW
+g = TW.tiny(seed=7)
+keys = TW.old_keys(g, 3)
+say("carried dense prior")
+upload(TW.carry(g, keys, *TW.WO.WindowOracle(g).marginalize(keys, g.var_state), g.var_state)).close()
+
 # sharded uploads of 40 frames per rank, the ranks as threads of this process (tests/test_gpu_multirank.py)
 import test_gpu_multirank as MR
 for world in (2, 3):
