@@ -493,6 +493,9 @@ __device__ __forceinline__ void error_body(const BlockView& B, int64_t i, const 
     res_linearized<T>(v, poses, points, B.consts + (int64_t)i * f_const(T), B.meas + (int64_t)i * f_dim(T), res);
 #pragma unroll
     for (int a = 0; a < f_dim(T); ++a) sq += res[a] * res[a];
+    // a container has no noise model: a constant that came with the block is ignored here as linearize_one ignores it
+    err_out[B.f0 + i] = 0.5 * sq;
+    return;
   } else if constexpr (f_dim(T) == 3) {
     double e[3], q[3], p[3], we[3];
     if constexpr (T == T_PTP) res_ptp(load_pose(poses + 12 * (int64_t)v[0]), points + 3 * (int64_t)v[1], B.meas + 3 * i, e, q);

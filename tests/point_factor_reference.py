@@ -73,14 +73,17 @@ times the largest absolute row sum of R for whitened quantities (tol()).
     LandmarkMotionPose  near       1.2e-15   0.0e+00   8.7e-11   5.0e-16
     LandmarkMotionPose  far        2.8e-12   0.0e+00   3.0e-07   1.5e-12
 """
+import copy
 import math
 
 import mpmath as mp
 import numpy as np
 
 if __package__:
+    from . import loss_reference as LR
     from . import se3_reference as SR
 else:                                     # `python tests/point_factor_reference.py`
+    import loss_reference as LR
     import se3_reference as SR
 
 mpf = mp.mpf
@@ -213,11 +216,16 @@ def numeric_jacobian(cls, X, meas, consts):
 
 
 # ---- noise -------------------------------------------------------------------------------------------------------------------
-def whiten(e, R, hk, strict=True):
+def whiten(e, R, hk, strict=True, kind=LR.HUBER):
     """R (3 x 3 of mpf) and Robust(Huber k) (hk <= 0: none): (R e, sqrt(w), the factor's error, |R e|); strict=False drops the
-    margin assertion (for a deliberately wrong R, whose |R e| may land anywhere)"""
+    margin assertion (for a deliberately wrong R, whose |R e| may land anywhere).  Another `kind` (loss_reference.KINDS) takes its
+    weight and loss from loss_reference, with that module's margin"""
     we = SR.mat_vec(R, e)
     n = mp.sqrt(sum(x * x for x in we))
+    if kind != LR.HUBER:
+        if hk > 0 and strict:
+            LR.check_margin(hk, n)
+        return we, mp.sqrt(LR.weight(kind, hk, n)), LR.loss(kind, hk, n), n
     if hk > 0:
         assert not strict or abs(n - hk) >= MARGIN * hk, "|Re| = %s within the margin of the Huber threshold %s" % (mp.nstr(n, 12), mp.nstr(hk, 12))
         w = mpf(1) if n <= hk else hk / n
@@ -235,8 +243,8 @@ def mat3(R):
 class Spec:
     """one factor of the table: its class, the fp64 numbers that cross the C ABI, and where in the table it sits"""
 
-    def __init__(self, cls, group, rep, entry, states, meas, consts, R, hk, jac=None):
-        self.cls, self.group, self.rep, self.entry = cls, group, rep, entry
+    def __init__(self, cls, group, rep, entry, states, meas, consts, R, hk, jac=None, kind=LR.HUBER):
+        self.cls, self.group, self.rep, self.entry, self.kind = cls, group, rep, entry, int(kind)
         self.jac = jac                    # the unwhitened Jacobian at `states` in 50 digits, where the builder already has it
         self.states = [np.asarray(s, dtype=np.float64) for s in states]
         self.meas = np.asarray(meas, dtype=np.float64).reshape(-1)
@@ -255,24 +263,43 @@ def unwhitened_jacobian(cls, X, meas, consts, cheirality):
 class Lin:
     """one linearised factor: unwhitened e and Ju, whitened and weighted J (3 x width, slots side by side) and b = -sqrt(w) R e,
     the factor's error, and what the tolerances need: scale (the largest absolute row sum of R), mag (the largest operand of the
-    residual), magJ (the largest entry of Ju)"""
+    residual), magJ (the largest entry of Ju).  The unweighted parts stay on the factor in 50 digits (we50 = R e, norm50 = |R e|,
+    RJu50 = R Ju), so that rewhitened() gives the same factor under another loss without differentiating again"""
 
-    def __init__(self, spec, states=None, want_J=True, R=None, strict=True):
+    def __init__(self, spec, states=None, want_J=True, R=None, strict=True, kind=None):
         cls = spec.cls
         X = states_of(cls, spec.states if states is None else states)
         mags = []
         e, self.cheirality = residual(cls, X, spec.meas, spec.consts, mags)
         Rm = mat3(spec.R if R is None else R)
-        we, sw, cost, n = whiten(e, Rm, mpf(spec.hk), strict)
+        self.kind, self.c = spec.kind if kind is None else int(kind), spec.hk
+        we, sw, cost, n = whiten(e, Rm, mpf(spec.hk), strict, self.kind)
         self.cls, self.group, self.numeric = cls, spec.group, cls == LMP
-        self.e, self.b, self.cost = SR.fl(e), SR.fl([-sw * x for x in we]), float(cost)
-        self.sqrt_w, self.norm, self.mag = float(sw), float(n), max(mags)
+        self.e, self.mag = SR.fl(e), max(mags)
+        self.we50, self.norm50, self.RJu50 = we, n, None
         self.scale = float(np.abs(np.asarray(spec.R if R is None else R, dtype=np.float64).reshape(3, 3)).sum(1).max())
         if want_J:
             Ju = spec.jac if states is None and spec.jac is not None else unwhitened_jacobian(cls, X, spec.meas, spec.consts, self.cheirality)
             self.Ju = np.array([[float(v) for v in row] for row in Ju])
-            self.J = np.array([[float(sw * sum(Rm[i][k] * Ju[k][c] for k in range(3))) for c in range(width(cls))] for i in range(3)])
+            self.RJu50 = [[sum(Rm[i][k] * Ju[k][c] for k in range(3)) for c in range(width(cls))] for i in range(3)]
             self.magJ = float(np.abs(self.Ju).max())
+        self._weigh(sw, cost)
+
+    def _weigh(self, sw, cost):
+        self.b, self.cost = SR.fl([-sw * x for x in self.we50]), float(cost)
+        self.sqrt_w, self.norm = float(sw), float(self.norm50)
+        if self.RJu50 is not None:
+            self.J = np.array([[float(sw * v) for v in row] for row in self.RJu50])
+
+    def rewhitened(self, kind, c, strict=True):
+        """this factor under Robust(kind, c) (c <= 0: none): a copy that shares the 50-digit unweighted parts.  Asserts
+        loss_reference's margin of the d <= c decision unless strict=False"""
+        out = copy.copy(self)
+        out.kind, out.c = int(kind), float(c)
+        if c > 0 and strict:
+            LR.check_margin(c, self.norm50)
+        out._weigh(mp.sqrt(LR.weight(kind, c, self.norm50)), LR.loss(kind, c, self.norm50))
+        return out
 
 
 def reference(specs, states=None, want_J=True):
@@ -359,7 +386,10 @@ def tol(lin, quantity):
 
 def robust_slack(lin):
     """An active Huber kernel scales J and b by sqrt(w) = sqrt(k / |Re|), which carries the residual's own rounding error:
-    d sqrt(w) / sqrt(w) = d|Re| / (2 |Re|), d|Re| <= sqrt(3) x the tolerance of one whitened entry.  Relative; 0 for w = 1."""
+    d sqrt(w) / sqrt(w) = d|Re| / (2 |Re|), d|Re| <= sqrt(3) x the tolerance of one whitened entry.  Relative; 0 for w = 1.
+    The other kinds: |d ln sqrt(w) / dd| of loss_reference.slack_coefficient in place of 1 / (2 |Re|)."""
+    if lin.kind != LR.HUBER:
+        return math.sqrt(3.0) * tol(lin, "e") * LR.slack_coefficient(lin.kind, lin.c, lin.norm)
     if lin.sqrt_w == 1.0:
         return 0.0
     return math.sqrt(3.0) * tol(lin, "e") / (2.0 * lin.norm)
@@ -368,6 +398,15 @@ def robust_slack(lin):
 def cost_tol(lin):
     """of a factor's error |Re|^2 / 2 (or its Huber loss, whose slope is no larger): |b|_1 x the tolerance of one whitened entry"""
     return float(np.abs(lin.b).sum()) * tol(lin, "cost") + 8.0 * EPS64 * lin.cost
+
+
+def loss_tols(lin):
+    """(relative, absolute): what a robust model of any kind adds to the tolerances of a factor's J and b (relative to their largest
+    entry: robust_slack plus the floor of sqrt(w)) and of its error (the floor of the loss formula, beside cost_tol, which stays
+    valid: it is |b|_1 x the tolerance of a whitened entry, and rho'(d) = w d <= sqrt(w) d)"""
+    if lin.c <= 0:
+        return 0.0, 0.0
+    return robust_slack(lin) + LR.FLOOR, LR.FLOOR * LR.loss_magnitude(lin.kind, lin.c, lin.norm)
 
 
 # ---- the input table ---------------------------------------------------------------------------------------------------------
@@ -481,17 +520,18 @@ def anchor(spec, pose_slot, point_slot, rng):
 X_CHR, L_CHR = ord("X") << 56, ord("l") << 56     # gtsam::Symbol('X', j) and ('l', j): chr in bits 56-63
 
 
-def pack(specs):
+def pack(specs, kind=None):
     """Plain arrays of a graph in which every factor of `specs` has variables of its own: (keys, var_type, var_state, var_of, blocks).
     Variables are in ascending key order (poses 'X' j, then points 'l' j, j the order of creation); var_of[f] lists the variable of
-    every slot of factor f; blocks are the runs of one class: (class, first factor, var_idx, meas, noise, huber_k, consts)"""
+    every slot of factor f; blocks are the runs of one class and loss kind: (class, first factor, var_idx, meas, noise, huber_k, consts,
+    kind); `kind` overrides the specs' own"""
     keys, vt, st, slots = [], [], [], []
     for sp in specs:
         mine = []
-        for kind, x in zip(SLOTS[sp.cls], sp.states):
+        for slot, x in zip(SLOTS[sp.cls], sp.states):
             j = len(keys)
-            keys.append((X_CHR if kind == "X" else L_CHR) | j)
-            vt.append(0 if kind == "X" else 1)
+            keys.append((X_CHR if slot == "X" else L_CHR) | j)
+            vt.append(0 if slot == "X" else 1)
             st.append(np.concatenate([x, np.zeros(12 - len(x))]))
             mine.append(j)
         slots.append(mine)
@@ -502,21 +542,23 @@ def pack(specs):
     blocks, f = [], 0
     while f < len(specs):
         g = f
-        while g < len(specs) and specs[g].cls == specs[f].cls:
+        while g < len(specs) and specs[g].cls == specs[f].cls and specs[g].kind == specs[f].kind:
             g += 1
         run = specs[f:g]
         blocks.append((run[0].cls, f, np.array(var_of[f:g]), np.array([s.meas for s in run]), np.array([s.R.reshape(-1) for s in run]),
-                       np.array([s.hk for s in run]), None if run[0].consts is None else np.array([s.consts for s in run])))
+                       np.array([s.hk for s in run]), None if run[0].consts is None else np.array([s.consts for s in run]),
+                       run[0].kind if kind is None else int(kind)))
         f = g
     return np.array(keys, dtype=np.uint64)[order], np.array(vt, dtype=np.uint8)[order], np.array(st)[order], var_of, blocks
 
 
 # ---- comparing a linearisation with the reference ----------------------------------------------------------------------------
-def flat_graph(specs):
-    """the dynosam_amd.graph.FlatGraph of pack(specs) (imported here only): one block per run of a class; returns (graph, var_of)"""
+def flat_graph(specs, kind=None):
+    """the dynosam_amd.graph.FlatGraph of pack(specs, kind) (imported here only): one block per run of a class and kind; returns
+    (graph, var_of)"""
     from dynosam_amd import graph as G
-    keys, vt, st, var_of, blocks = pack(specs)
-    fb = [G.FactorBlock(cls, np.arange(f0, f0 + len(var)), var, meas, noise, hk, consts) for cls, f0, var, meas, noise, hk, consts in blocks]
+    keys, vt, st, var_of, blocks = pack(specs, kind)
+    fb = [G.FactorBlock(cls, np.arange(f0, f0 + len(var)), var, meas, noise, hk, consts, k) for cls, f0, var, meas, noise, hk, consts, k in blocks]
     return G.FlatGraph(keys, vt, st, fb), var_of
 
 

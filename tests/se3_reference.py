@@ -54,11 +54,17 @@ the residual's tolerance x 1 / (2 delta) = 5e4 (its own measured error is listed
 The factor e of the small regimes is the rounding of the O(1) states the relative pose is formed from, not of the logarithm.)
 """
 import contextlib
+import copy
 import math
 from collections import Counter
 
 import mpmath as mp
 import numpy as np
+
+if __package__:
+    from . import loss_reference as LR
+else:                                     # `python tests/se3_reference.py`
+    import loss_reference as LR
 
 mp.mp.dps = 50
 mpf = mp.mpf
@@ -323,10 +329,15 @@ def true_log(T):
 
 
 # ---- noise models and factors (dev_factors.h) ------------------------------------------------------------------------------
-def whiten(e, sigmas, hk):
-    """6 sigmas and Robust(Huber k) (hk <= 0: none): (whitened e, sqrt(w), the factor's error)"""
+def whiten(e, sigmas, hk, kind=LR.HUBER):
+    """6 sigmas and Robust(Huber k) (hk <= 0: none): (whitened e, sqrt(w), the factor's error); another `kind`
+    (loss_reference.KINDS) takes its weight and loss from loss_reference, with that module's margin of the d <= c decision"""
     we = [e[i] / sigmas[i] for i in range(6)]
     n = mp.sqrt(sum(x * x for x in we))
+    if kind != LR.HUBER:
+        if hk > 0:
+            LR.check_margin(hk, n)
+        return we, mp.sqrt(LR.weight(kind, hk, n)), LR.loss(kind, hk, n)
     if hk > 0:
         w = mpf(1) if n <= hk else hk / n
         loss = n * n / 2 if n <= hk else hk * (n - hk / 2)
@@ -337,38 +348,56 @@ def whiten(e, sigmas, hk):
 
 class Lin:
     """one linearised factor: unwhitened residual e, whitened blocks J (6 x 6 per variable, concatenated), b = -sqrt(w) W e, the
-    factor's error, the branches taken and - for numeric Jacobians - whether the central difference stayed inside them"""
+    factor's error, the branches taken and - for numeric Jacobians - whether the central difference stayed inside them.  The
+    unweighted parts stay on the factor in 50 digits (we50 = W e, norm50 = |W e|, WJ50 = W J), so that rewhitened() gives the same
+    factor under another loss without differentiating again"""
 
-    def __init__(self, e, blocks, sigmas, hk, trace, jac_ok=True):
-        we, sw, cost = whiten(e, sigmas, hk)
+    def __init__(self, e, blocks, sigmas, hk, trace, jac_ok=True, kind=LR.HUBER):
+        we, sw, cost = whiten(e, sigmas, hk, kind)
+        self.kind, self.c = int(kind), float(hk)
         self.e = fl(e)
-        self.b = fl([-sw * x for x in we])
-        self.J = np.array([[float(sw * B[i][j] / sigmas[i]) for B in blocks for j in range(6)] for i in range(6)])
-        self.cost = float(cost)
+        self.we50, self.norm50 = we, mp.sqrt(sum(x * x for x in we))
+        self.WJ50 = [[B[i][j] / sigmas[i] for B in blocks for j in range(6)] for i in range(6)]
         self.scale = float(max(1 / s for s in sigmas))
-        self.sqrt_w, self.norm = float(sw), float(mp.sqrt(sum(x * x for x in we)))
         self.trace = trace
         self.jac_ok = jac_ok
+        self._weigh(sw, cost)
+
+    def _weigh(self, sw, cost):
+        self.b = fl([-sw * x for x in self.we50])
+        self.J = np.array([[float(sw * v) for v in row] for row in self.WJ50])
+        self.cost = float(cost)
+        self.sqrt_w, self.norm = float(sw), float(self.norm50)
+
+    def rewhitened(self, kind, c, strict=True):
+        """this factor under Robust(kind, c) (c <= 0: none): a copy that shares the 50-digit unweighted parts.  Asserts
+        loss_reference's margin of the d <= c decision unless strict=False"""
+        out = copy.copy(self)
+        out.kind, out.c = int(kind), float(c)
+        if c > 0 and strict:
+            LR.check_margin(c, self.norm50)
+        out._weigh(mp.sqrt(LR.weight(kind, c, self.norm50)), LR.loss(kind, c, self.norm50))
+        return out
 
 
 def _eye6(s=1):
     return [[mpf(s * int(i == j)) for j in range(6)] for i in range(6)]
 
 
-def prior(x, p, sigmas, hk=0.0):
+def prior(x, p, sigmas, hk=0.0, kind=LR.HUBER):
     """PriorFactor<Pose3>: e = -Log(x^-1 prior), J = I"""
     with recording() as rec:
         l, _ = local(pose(x), pose(p))
-    return Lin([-v for v in l], [_eye6()], vec(sigmas), mpf(float(hk)), rec.trace)
+    return Lin([-v for v in l], [_eye6()], vec(sigmas), mpf(float(hk)), rec.trace, kind=kind)
 
 
-def between_factor(p1, p2, meas, sigmas, hk=0.0):
+def between_factor(p1, p2, meas, sigmas, hk=0.0, kind=LR.HUBER):
     """BetweenFactor<Pose3>: e = Log(meas^-1 P1^-1 P2), J1 = -Ad(hx^-1), J2 = I"""
     with recording() as rec:
         hx = between(pose(p1), pose(p2))
         e, _ = local(pose(meas), hx)
     A = adjoint(inverse(hx))
-    return Lin(e, [[[-A[i][j] for j in range(6)] for i in range(6)], _eye6()], vec(sigmas), mpf(float(hk)), rec.trace)
+    return Lin(e, [[[-A[i][j] for j in range(6)] for i in range(6)], _eye6()], vec(sigmas), mpf(float(hk)), rec.trace, kind=kind)
 
 
 def smooth_residual(P, Le):
@@ -383,7 +412,7 @@ def lps_residual(P, _unused=None):
     return se3_log(between(a, b))[0]
 
 
-def numeric_factor(residual, states, const, sigmas, hk=0.0, want_J=True):
+def numeric_factor(residual, states, const, sigmas, hk=0.0, want_J=True, kind=LR.HUBER):
     """a factor whose Jacobians are gtsam::numericalDerivative3x: central differences with delta = 1e-5 on the manifold.
     jac_ok: all 36 perturbed residuals took the branches of the unperturbed one, each at least MARGIN away from its thresholds -
     otherwise the difference straddles a discontinuity of the logarithm and compares nothing meaningful."""
@@ -409,15 +438,15 @@ def numeric_factor(residual, states, const, sigmas, hk=0.0, want_J=True):
             blocks.append(B)
     else:
         blocks = [_eye6(0)] * 3
-    return Lin(e, blocks, vec(sigmas), mpf(float(hk)), rec.trace, ok)
+    return Lin(e, blocks, vec(sigmas), mpf(float(hk)), rec.trace, ok, kind)
 
 
-def smoothing_factor(states, Le, sigmas, hk=0.0, want_J=True):
-    return numeric_factor(smooth_residual, states, Le, sigmas, hk, want_J)
+def smoothing_factor(states, Le, sigmas, hk=0.0, want_J=True, kind=LR.HUBER):
+    return numeric_factor(smooth_residual, states, Le, sigmas, hk, want_J, kind)
 
 
-def lps_factor(states, sigmas, hk=0.0, want_J=True):
-    return numeric_factor(lps_residual, states, None, sigmas, hk, want_J)
+def lps_factor(states, sigmas, hk=0.0, want_J=True, kind=LR.HUBER):
+    return numeric_factor(lps_residual, states, None, sigmas, hk, want_J, kind)
 
 
 def linearized(A, lins, xs, b):
@@ -509,7 +538,10 @@ def tol(regime, quantity, magnitude=1.0, scale=1.0):
 
 def robust_slack(lin, regime):
     """An active Huber kernel scales J and b by sqrt(w) = sqrt(k / |We|), which carries the residual's own rounding error:
-    d sqrt(w) / sqrt(w) = d|We| / (2 |We|), d|We| <= sqrt(6) x the tolerance of one whitened entry.  Relative; 0 for w = 1."""
+    d sqrt(w) / sqrt(w) = d|We| / (2 |We|), d|We| <= sqrt(6) x the tolerance of one whitened entry.  Relative; 0 for w = 1.
+    The other kinds: |d ln sqrt(w) / dd| of loss_reference.slack_coefficient in place of 1 / (2 |We|)."""
+    if lin.kind != LR.HUBER:
+        return math.sqrt(6.0) * tol(regime, "e", np.abs(lin.e).max(), lin.scale) * LR.slack_coefficient(lin.kind, lin.c, lin.norm)
     if lin.sqrt_w == 1.0:
         return 0.0
     return math.sqrt(6.0) * tol(regime, "e", np.abs(lin.e).max(), lin.scale) / (2.0 * lin.norm)
@@ -518,6 +550,15 @@ def robust_slack(lin, regime):
 def cost_tol(lin, regime):
     """of a factor's error 0.5 |We|^2 (or its Huber loss, whose slope is no larger): |We|_1 x the tolerance of one whitened entry"""
     return float(np.abs(lin.b).sum()) * tol(regime, "e", np.abs(lin.e).max(), lin.scale) + 8.0 * EPS64 * lin.cost
+
+
+def loss_tols(lin, regime):
+    """(relative, absolute): what a robust model of any kind adds to the tolerances of a factor's J and b (relative to their largest
+    entry: robust_slack plus the floor of sqrt(w)) and of its error (the floor of the loss formula, beside cost_tol, which stays
+    valid: it is |b|_1 x the tolerance of a whitened entry, and rho'(d) = w d <= sqrt(w) d)"""
+    if lin.c <= 0:
+        return 0.0, 0.0
+    return robust_slack(lin, regime) + LR.FLOOR, LR.FLOOR * LR.loss_magnitude(lin.kind, lin.c, lin.norm)
 
 
 # ---- states that put a factor's relative pose at a table entry ----------------------------------------------------------------

@@ -30,8 +30,9 @@ def keys_for(n):
     return np.array([S.CameraPoseSymbol(i) for i in range(n)], dtype=np.uint64)
 
 
-def graph_of(classes):
-    """one block per class, REPLICAS x 40 factors each, replica-major; every factor on variables of its own"""
+def graph_of(classes, kind=0, hk_of=None):
+    """one block per class, REPLICAS x 40 factors each, replica-major; every factor on variables of its own.  kind: the blocks' loss
+    kind; hk_of(class, replica, entry index): the robust constant in place of the fixed 1.0 / 1e3 of replicas 1 / 3"""
     rng = np.random.default_rng(77)
     states, blocks = [], []
     for t in classes:
@@ -54,14 +55,14 @@ def graph_of(classes):
                 var.append(list(range(v0, v0 + len(st))))
                 meas.append(m)
                 consts.append(c)
-                hk.append({1: 1.0, 3: 1e3}.get(rep, 0.0))
+                hk.append({1: 1.0, 3: 1e3}.get(rep, 0.0) if hk_of is None else hk_of(t, rep, len(var) - 1 - rep * len(SR.regimes())))
         n = len(var)
         blocks.append(G.FactorBlock(t, np.arange(n), var, np.array(meas), np.tile(SIGMAS[t], (n, 1)), np.array(hk),
-                                    np.array(consts) if consts[0] is not None else None))
+                                    np.array(consts) if consts[0] is not None else None, kind))
     return G.FlatGraph(keys_for(len(states)), np.zeros(len(states), np.uint8), np.array(states), blocks)
 
 
-def reference(g, state=None, jac=True):
+def reference(g, state=None, jac=True, jac_replicas=JAC_REPLICAS):
     """se3_reference's linearisation of every factor of g at `state` (default: the graph's own), in the order of linearize()"""
     st = g.var_state if state is None else state
     out = []
@@ -69,15 +70,15 @@ def reference(g, state=None, jac=True):
         for i in range(blk.count):
             x = [st[v] for v in blk.var_idx[i]]
             hk = 0.0 if blk.huber_k is None else blk.huber_k[i]
-            want = jac and i < JAC_REPLICAS * len(SR.regimes())
+            want = jac and i < jac_replicas * len(SR.regimes())
             if blk.type == G.F_PRIOR_POSE3:
-                out.append(SR.prior(x[0], blk.meas[i], blk.noise[i], hk))
+                out.append(SR.prior(x[0], blk.meas[i], blk.noise[i], hk, blk.loss))
             elif blk.type == G.F_BETWEEN_POSE3:
-                out.append(SR.between_factor(x[0], x[1], blk.meas[i], blk.noise[i], hk))
+                out.append(SR.between_factor(x[0], x[1], blk.meas[i], blk.noise[i], hk, blk.loss))
             elif blk.type == G.F_HYBRID_SMOOTHING:
-                out.append(SR.smoothing_factor(x, blk.consts[i], blk.noise[i], hk, want))
+                out.append(SR.smoothing_factor(x, blk.consts[i], blk.noise[i], hk, want, blk.loss))
             else:
-                out.append(SR.lps_factor(x, blk.noise[i], hk, want))
+                out.append(SR.lps_factor(x, blk.noise[i], hk, want, blk.loss))
             out[-1].type, out[-1].has_J = blk.type, want or blk.type not in NUMERIC
     return out
 
